@@ -14,7 +14,11 @@ bf16), egalitarian welfare, END TO END: one step = one full N x A scoring pass,
 i.e. what one reference `_calculate_candidate_rewards` + `_calculate_egalitarian_welfare`
 (src/methods/best_of_n.py:240-418) costs with every get_prompt_logprobs call
 (src/utils.py:201-281) served locally.  `value` = agent x candidate scorings/s of the
-whole job.  The same line carries:
+whole job, `ms_per_step` = milliseconds per timed pass (`--steps` of them after `--warmup`).
+A plain run times this leg alone.  `--dump-outputs DIR` writes what its last timed pass
+returned (best_candidate, welfare [N], utilities [A, N], token_logprobs [A * N * T]) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+With `--full` the same line also carries:
   kernel_only     the post-LM-head path alone on resident logits (76,800 x 128,256 bf16 =
                   19.7 GB per pass); `roofline` prices its dominant kernel
                   (lsg_stream_kernel of cs_logsoftmax_gather) against 8 TB/s from HIP
@@ -172,6 +176,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (kernel_only + roofline, beam_kernel, the "
+                         "product-API Best-of-N pass, method_decode, cpu_baseline); a plain run "
+                         "times the headline leg only and ignores those legs' options")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg's last step computed "
+                         "as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS),
                     help="workload of the kernel-only leg")
     ap.add_argument("--e2e", default=1, type=int,
@@ -203,7 +214,10 @@ def parse():
                          "communicator): the per-GPU shapes of BASELINE's 8-GPU configs")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "pmc_traffic.json"),
                     help="rocprofv3 PMC summary giving HBM bytes per launch (optional)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -328,9 +342,29 @@ def make_inputs(A, N, T, V, seed, dev):
     return logits, tgt, offsets
 
 
-def c2_kernel_leg(args, world, rank, dev):
+def _as_np(t):
+    """A tensor as the float32 / float64 NumPy array written by --dump-outputs."""
+    wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+    return t.detach().to("cpu", torch.float64 if wide else torch.float32).numpy()
+
+
+def dump_outputs(out_dir, arrays, cap_bytes=64 << 20, seed=0):
+    """Write every array as out_dir/<name>.npy; an array over its share of ``cap_bytes``
+    is cut to a fixed, seeded sample of its flattened elements (in index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = cap_bytes // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > share:
+            keep = np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def c2_kernel_leg(args, world, rank, dev, outputs=None):
     """The post-LM-head path alone on resident logits (BASELINE C2 / C4 shapes):
-    cs_logsoftmax_gather -> cs_segment_reduce -> mean -> welfare -> [all-reduce] -> top-1."""
+    cs_logsoftmax_gather -> cs_segment_reduce -> mean -> welfare -> [all-reduce] -> top-1.
+    ``outputs`` (a dict) receives the last timed step's results as NumPy arrays."""
     ops = importlib.import_module(PKG_DIR + ".ops")
     par = importlib.import_module(PKG_DIR + ".parallel")
     A, N, T, V, wkind, desc = CONFIGS[args.config]
@@ -366,7 +400,7 @@ def c2_kernel_leg(args, world, rank, dev):
         if ev is not None:
             ev[3].record(stream)
         idx, _ = ops.topk(W, 1)
-        return idx
+        return idx, W, U, tok
 
     for _ in range(args.warmup):
         step()
@@ -375,9 +409,12 @@ def c2_kernel_leg(args, world, rank, dev):
     _barrier_sync(world)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(events[i])
+        last = step(events[i])
     _barrier_sync(world)
     elapsed = _max_over_ranks(time.perf_counter() - t0, world, dev)
+    if outputs is not None:
+        outputs.update(zip(("best_candidate", "welfare", "utilities", "token_logprobs"),
+                           map(_as_np, last)))
     kern_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
     coll_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in events]))
     ms = elapsed * 1000.0 / args.steps
@@ -409,10 +446,11 @@ def _model_flops_per_token(cfg):
     return 2.0 * (L * per_layer + cfg.vocab * d)
 
 
-def c2_e2e_leg(args, world, rank, dev, prefix_len=200, seed=0):
+def c2_e2e_leg(args, world, rank, dev, outputs=None, prefix_len=200, seed=0):
     """BASELINE C2 end to end: Llama-3.1-8B (random init, bf16) prefills the A agent prefixes,
     scores N candidates x T tokens under every agent (shared prefix K/V on the stream
-    kernels), LM head, HIP kernels, welfare (+ RCCL MIN all-reduce), selection."""
+    kernels), LM head, HIP kernels, welfare (+ RCCL MIN all-reduce), selection.
+    ``outputs`` (a dict) receives the last timed pass's results as NumPy arrays."""
     M = importlib.import_module(PKG_DIR + ".model")
     E = importlib.import_module(PKG_DIR + ".engine")
     ops = importlib.import_module(PKG_DIR + ".ops")
@@ -439,16 +477,20 @@ def c2_e2e_leg(args, world, rank, dev, prefix_len=200, seed=0):
         seg = ops.segment_reduce(lp, offs)
         U = (seg["sum_lp"] / seg["count"].to(torch.float32)).view(A, N).contiguous()
         W = par.combine_welfare(U, wkind, shard, nonfinite="replace")
-        return ops.topk(W, 1)[0]
+        return ops.topk(W, 1)[0], W, U, lp
 
     for _ in range(args.warmup):
         one_pass()
     _barrier_sync(world)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_pass()
+        last = one_pass()
     _barrier_sync(world)
     el = _max_over_ranks(time.perf_counter() - t0, world, dev)
+    if outputs is not None:
+        outputs.update(zip(("best_candidate", "welfare", "utilities", "token_logprobs"),
+                           map(_as_np, last)))
+    del last
     dt = el / args.steps
     tokens = A * N * T + A * prefix_len
     flops = _model_flops_per_token(cfg) * tokens
@@ -1249,11 +1291,18 @@ def main():
             _free()
             return None
 
-    _progress("kernel_only")
-    kern = c2_kernel_leg(args, world, rank, dev)
-    _free()
+    # the headline leg is the forward-included C2 pass, or (--e2e 0 / another --config) the
+    # kernel-only leg; a plain run times that leg alone, --full every other leg as well
+    headline_e2e = bool(args.e2e) and args.config == "c2"
+    dumping = bool(args.dump_outputs) and rank == 0
+    kern_out, e2e_out = ({}, {}) if dumping else (None, None)
+    kern = None
+    if args.full or not headline_e2e:
+        _progress("kernel_only")
+        kern = c2_kernel_leg(args, world, rank, dev, kern_out)
+        _free()
     beam = {}
-    beams = [b for b in args.beam.split(",") if b]
+    beams = [b for b in args.beam.split(",") if b] if args.full else []
     comm = None
     if beams and torch.distributed.is_initialized() and args.backend == "nccl":
         try:
@@ -1270,22 +1319,28 @@ def main():
     if comm is not None:
         comm.close()
     _free()
-    _progress("end_to_end")
-    e2e = (guarded("end_to_end", c2_e2e_leg, args, world, rank, dev)
-           if args.e2e and args.config == "c2" else None)
+    e2e = None
+    if headline_e2e:
+        _progress("end_to_end")
+        # --full: a failing leg is reported in the line and the kernel-only leg stands in
+        # as the (labelled) headline; a plain run has no other leg, so it fails
+        e2e = (guarded("end_to_end", c2_e2e_leg, args, world, rank, dev, e2e_out) if args.full
+               else c2_e2e_leg(args, world, rank, dev, e2e_out))
+    if dumping:   # the headline leg's last timed step
+        dump_outputs(args.dump_outputs, e2e_out if e2e is not None else kern_out)
     method = {}
-    if args.e2e and args.config == "c2" and args.method_bon:
+    if args.full and headline_e2e and args.method_bon:
         _progress("method_bon.c2")
         r = guarded("method_bon.c2", method_leg_bon, args, world, rank, dev)
         if r is not None:
             method["c2_best_of_n"] = r
-    for name in [m for m in args.method.split(",") if m]:
+    for name in [m for m in args.method.split(",") if m] if args.full else []:
         _progress("method_decode." + name)
         r = guarded("method_decode." + name, method_leg, name, args, world, rank, dev)
         if r is not None:
             method[name] = r
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         _progress("cpu_baseline")
         cpu = guarded("cpu_baseline", cpu_baseline, args.cpu_seconds)
 
@@ -1323,10 +1378,15 @@ def main():
                        "parallelism": f"agents sharded over {world} GPU(s)"},
             "gemm_tuning": (os.path.relpath(gemm_tuning, os.path.dirname(os.path.abspath(__file__)))
                             if gemm_tuning else None),
-            "roofline": kern["roofline"],
-            "cpu_baseline": cpu,
-            "kernel_only": {k: v for k, v in kern.items() if k != "roofline"},
+            "full": bool(args.full),
         }
+        if args.full:
+            line["cpu_baseline"] = cpu
+        if kern is not None:
+            line["roofline"] = kern["roofline"]
+            line["kernel_only"] = {k: v for k, v in kern.items() if k != "roofline"}
+        if dumping:
+            line["dumped_outputs"] = sorted(e2e_out if e2e is not None else kern_out)
         if e2e is not None:
             line["end_to_end"] = e2e
         if method:

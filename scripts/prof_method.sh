@@ -14,7 +14,7 @@ TAG="$TAG${SUFFIX:-}"
 for c in "$@"; do
   D="$R/gpurun_out/prof_method_$c$TAG"
   (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$D" -o run -f csv -- \
-     python3 "$R/bench.py" --steps 1 --warmup 0 --cpu-seconds 0 --e2e 0 --beam "" --method "$c" \
+     python3 "$R/bench.py" --full --steps 1 --warmup 0 --cpu-seconds 0 --e2e 0 --beam "" --method "$c" \
        --method-bon 0 --method-text-steps 0 $EXTRA > "$D.log" 2>&1) || exit $?
   python3 "$R/scripts/trace_by_grid.py" "$D/run_kernel_trace.csv" > "$D/by_grid.csv" || exit $?
   rm -f "$D/run_kernel_trace.csv"

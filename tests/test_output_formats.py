@@ -1,14 +1,14 @@
 """§8(f) row 4 — output formats: the evaluator's file-level path writes
 evaluation_results.csv in the reference's layout (column schema of the published
-file), and the reference's own improved_aggregation consumes it (checked in the build
-container, where /root/reference exists).  Kernels are emulated by the oracle here
-(host logic only); tests/test_methods_gpu.py covers the same evaluator on the MI355X."""
+file), and it still carries what the reference's own improved_aggregation consumed from
+it (checked against the table that aggregator wrote, stored with the fixture).  Kernels
+are emulated by the oracle here (host logic only); tests/test_methods_gpu.py covers the
+same evaluator on the MI355X."""
 import importlib
 import math
 import os
+import re
 import shutil
-import subprocess
-import sys
 
 import pandas as pd
 import pytest
@@ -62,18 +62,32 @@ def test_evaluation_csv_welfare_identities(evaluated):
         assert abs(r["log_nash_welfare_perplexity"] - sum(r[f"avg_logprob_{a}"] for a in agents)) < 1e-3
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"),
-                    reason="the reference's aggregator exists only in the build container")
-def test_reference_improved_aggregation_consumes_our_output(evaluated, tmp_path):
+def test_reference_improved_aggregation_consumes_our_output(evaluated):
+    """golden/results_fixture/reference_aggregated_metrics.csv is the table the reference's
+    improved_aggregation wrote when it was run on this fixture's evaluation_results.csv
+    (one row per method key, mean and population std over the seeds of every perplexity
+    column it picked up).  What it consumed must still be in our file: the same method
+    keys from ``method`` / ``method_with_params``, every column it aggregated, and values
+    that fold to the recorded numbers.  Tolerance: the fixture model's fp32 CPU forward
+    moves a mean log-prob by ~1e-6 with the summation order (thread count), i.e. a
+    perplexity by ~1e-6 relative; 1e-4 of the column's mean is far above that and far
+    below the seed-to-seed spread the std columns measure."""
     run, out, _ = evaluated
-    code = ("import sys; sys.dont_write_bytecode=True; sys.path.insert(0, '/root/reference'); "
-            "import improved_aggregation as ia; ia.main([sys.argv[1]])")
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", MPLBACKEND="Agg")
-    p = subprocess.run([sys.executable, "-c", code, str(run)], cwd=tmp_path, env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    agg = run / "evaluation" / "improved_aggregate" / "aggregated_metrics.csv"
-    assert agg.exists(), p.stdout[-2000:] + p.stderr[-2000:]
-    df = pd.read_csv(agg)
-    assert len(df) >= 1
-    assert any("perplexity" in c for c in df.columns)
+    ours = pd.read_csv(out / "evaluation_results.csv")
+    ref = pd.read_csv(os.path.join(FIX, "reference_aggregated_metrics.csv"))
+    assert len(ref) >= 1
+    metrics = [c[:-len("_mean")] for c in ref.columns if c.endswith("_mean")]
+    assert metrics and all("perplexity" in m for m in metrics)
+    assert all(m in ours.columns and m + "_std" in ref.columns for m in metrics)
+    # the aggregator's method key: method_with_params without its "[seed=...]" suffix
+    key = ours["method_with_params"].str.replace(r"\s*\[seed=\d+\]$", "", regex=True)
+    assert sorted(key.unique()) == sorted(ref["method_with_params"])
+    for _, r in ref.iterrows():
+        rows = ours[key == r["method_with_params"]]
+        assert (rows["method"] == r["method"]).all()
+        assert re.search(r"beam_width=(\d+)", r["method_with_params"]).group(1) == \
+            str(r["param_beam_width"])
+        for m in metrics:
+            tol = 1e-4 * abs(r[m + "_mean"])
+            assert abs(rows[m].mean() - r[m + "_mean"]) <= tol, (r["method_with_params"], m)
+            assert abs(rows[m].std(ddof=0) - r[m + "_std"]) <= tol, (r["method_with_params"], m)

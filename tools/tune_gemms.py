@@ -54,8 +54,8 @@ def main() -> int:
             for m in args.legs.split(",") if m]
     rc = 0
     for name, extra in legs:
-        cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup",
-               "1", "--beam", "", "--cpu-seconds", "0"] + extra
+        cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--full", "--steps", "2",
+               "--warmup", "1", "--beam", "", "--cpu-seconds", "0"] + extra
         t0 = time.time()
         p = subprocess.Popen(cmd, env=env, cwd=REPO)
         while p.poll() is None:
