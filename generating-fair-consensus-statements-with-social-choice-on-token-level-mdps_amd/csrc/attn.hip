@@ -1,6 +1,6 @@
 // attn.hip — the transformer side of the batched agent x candidate decode:
 //
-//   prefix_attn_kernel   cascade attention over SHARED per-agent prefix K/V.  Every
+//   prefix_attn_*_kernel cascade attention over SHARED per-agent prefix K/V.  Every
 //                        candidate stream of an agent (a beam, a Best-of-N candidate) reads
 //                        its agent's prefix keys through one workgroup that holds ALL of
 //                        that agent's query rows of one K/V head, so a prefix key block is
@@ -56,13 +56,10 @@ constexpr int kMaxSplit = 32;       // key splits of one (group, head, query gro
 constexpr int kPlanMinBase = 1024;  // from this many (group, head, query group) workgroups on,
                                     // the chip is full without key splits: no plan
 constexpr int kMergeRows = 8;       // query rows per merge workgroup (2 per wave)
-#ifndef CS_ATTN_LAZY
-#define CS_ATTN_LAZY 8.0f           // attend_block's lazy-rescale threshold (log2 units; 0: every block)
-#endif
-constexpr float kLazyRescale = CS_ATTN_LAZY;
+constexpr float kLazyRescale = 8.0f;   // attend_block's lazy-rescale threshold (log2 units)
 constexpr int64_t kPlanImbalance = 4;   // ... or from a longest cell 4x the mean on (T = 1)
-constexpr int kTargetWgsDefault = 512;    // plan: split cells until about this many workgroups
-constexpr int kMinItemsDefault = 3;       // ... but never below this many key blocks per wave
+constexpr int kPlanTargetWgs = 512;     // plan: split cells until about this many workgroups
+constexpr int kPlanMinItems = 3;        // ... but never below this many key blocks per wave
 
 // Work plan entries (int32 x 4, device memory), attention entries first:
 //   attention  {pg = group * Hkv + head, query group, split | n_used << 8, partial slot}
@@ -245,193 +242,15 @@ __device__ __forceinline__ void attend_block(const AttnParams& a, const KeyBlock
   }
 }
 
-// PF: register double buffering (the next block's loads in flight while the current one
-// is attended) for the latency-bound decode launches (few workgroups, a plan); without it
-// the kernel holds fewer registers and more waves per SIMD, which serves the many-workgroup
-// scoring launches (T > 1) better.
-template <int D, bool PF>
-__global__ __launch_bounds__(kAttnThreads, PF ? (D <= 128 ? 2 : 1) : (D <= 128 ? 3 : 2))
-void prefix_attn_kernel(AttnParams a) {
-  constexpr int NDS = D / 32;   // 32-wide d steps of S^T = K . Q^T
-  constexpr int NDT = D / 16;   // 16-row d tiles of O^T
-  constexpr int LDSW = D + 2;   // per query row: O[D], m, l
-  __shared__ float sm[3][16][LDSW];
-
-  int pg, qg, split, n_used, slot;
-  if (a.plan) {
-    const int4 e = a.plan[blockIdx.x];
-    pg = e.x;
-    qg = e.y;
-    split = e.z & 255;
-    n_used = e.z >> 8;
-    slot = e.w;
-  } else {
-    const int bid = logical_block(a.swizzle);
-    qg = bid % a.n_qg;
-    pg = bid / a.n_qg;
-    split = 0;
-    n_used = 1;
-    slot = 0;
-  }
-  const int gi = pg / a.Hkv, g = pg % a.Hkv;
-  const int p = a.gpfx ? a.gpfx[gi] : gi;
-  const int M = a.n_str * a.T * a.rep;
-  const int r0 = qg * kGroupRows;
-  const int nrows = min(kGroupRows, M - r0);
-  const int n_qt = (nrows + 15) >> 4;
-  const int kw = n_qt == 1 ? 4 : (n_qt == 2 ? 2 : 1);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int qt = w % n_qt, ks = w / n_qt;
-  const bool active = ks < kw;
-  const int col = lane & 15, h4 = lane >> 4;
-
-  const int row = r0 + qt * 16 + col;
-  const bool vrow = active && row < M;
-  const int rr = row < M ? row : M - 1;
-  const int jh = rr % a.rep, bt = rr / a.rep;
-  const int t = bt % a.T, b = bt / a.T;
-  const int64_t s = static_cast<int64_t>(gi) * a.n_str + b;
-  const int64_t tok = s * a.T + t;
-  const int head = g * a.rep + jh;
-  const int hb = *a.hist_base;
-  const int pl = a.plen[p];
-  const int64_t po = a.poff[p];
-  const int hv = min(hb + t + 1, static_cast<int>(a.ldh));
-  // sliding window (Gemma-2 even layers): key position > qpos - window; prefix key j sits at
-  // position j, history slot j at pl + j, the query at pl + hb + t
-  const int kmin_pos = a.window > 0 ? pl + hb + t - a.window + 1 : INT32_MIN;
-
-  // the tile's streams (wave-uniform)
-  const int rt0 = r0 + qt * 16, rt1 = min(rt0 + 15, M - 1);
-  const int b_lo = (rt0 / a.rep) / a.T, b_hi = (rt1 / a.rep) / a.T;
-  const int t_hi = b_lo == b_hi ? (rt1 / a.rep) % a.T : a.T - 1;
-  const int nbh = (min(hb + t_hi + 1, static_cast<int>(a.ldh)) + kKeyBlock - 1) / kKeyBlock;
-  const int nbp = (pl + kKeyBlock - 1) / kKeyBlock;
-  const int n_items = nbp + (b_hi - b_lo + 1) * nbh;
-
-  bf16x8 qf[NDS];
-  {
-    const __bf16* qrow = a.q + (tok * a.H + head) * D + 8 * h4;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) {
-      if (vrow) {
-        qf[ds] = *reinterpret_cast<const bf16x8*>(qrow + ds * 32);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qf[ds][e] = static_cast<__bf16>(0.0f);
-      }
-    }
-  }
-
-  f32x4 o[NDT];
-#pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m = -INFINITY, l = 0.0f;
-
-  // the wave's blocks it0, it0 + nslot, ...: two register buffers, the next block's loads
-  // in flight while the current one is attended (a wave issues ONE round trip per block,
-  // overlapped with the previous block's MFMA / softmax work).  The last block's
-  // "next" is itself again (an L2 hit) so the loop body has no branch around the loads.
-  const int nslot = n_used * kw;
-  int it = split * kw + ks;
-  if (!PF && active) {
-    for (; it < n_items; it += nslot) {
-      KeyBlock<D> f;
-      const ItemRef r = item_ref(a, it, nbp, nbh, b_lo, b, gi, g, po, pl, hv, vrow, col, h4, D);
-      load_block<D>(f, r);
-      attend_block<D>(a, f, r, qf, kmin_pos, h4, o, m, l);
-    }
-  } else if (active && it < n_items) {
-    KeyBlock<D> fa, fb;
-    ItemRef ra = item_ref(a, it, nbp, nbh, b_lo, b, gi, g, po, pl, hv, vrow, col, h4, D), rb;
-    load_block<D>(fa, ra);
-    while (true) {
-      int itn = it + nslot < n_items ? it + nslot : it;
-      rb = item_ref(a, itn, nbp, nbh, b_lo, b, gi, g, po, pl, hv, vrow, col, h4, D);
-      load_block<D>(fb, rb);
-      __builtin_amdgcn_sched_barrier(0);
-      attend_block<D>(a, fa, ra, qf, kmin_pos, h4, o, m, l);
-      it += nslot;
-      if (it >= n_items) break;
-      itn = it + nslot < n_items ? it + nslot : it;
-      ra = item_ref(a, itn, nbp, nbh, b_lo, b, gi, g, po, pl, hv, vrow, col, h4, D);
-      load_block<D>(fa, ra);
-      __builtin_amdgcn_sched_barrier(0);
-      attend_block<D>(a, fb, rb, qf, kmin_pos, h4, o, m, l);
-      it += nslot;
-      if (it >= n_items) break;
-    }
-  }
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
-
-  // waves that share a query tile combine through LDS (fixed order: ks = 0, 1, ...)
-  if (kw > 1) {
-    if (active && ks > 0) {
-      const int sl = w - n_qt;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sm[sl][col][dt * 16 + 4 * h4 + i] = o[dt][i];
-      if (h4 == 0) {
-        sm[sl][col][D] = m;
-        sm[sl][col][D + 1] = l;
-      }
-    }
-    __syncthreads();
-    if (active && ks == 0) {
-      float mt = m;
-      for (int k = 1; k < kw; ++k) mt = fmaxf(mt, sm[qt + n_qt * k - n_qt][col][D]);
-      const float c0 = mt == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(m - mt);
-      l *= c0;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) o[dt] *= c0;
-      for (int k = 1; k < kw; ++k) {
-        const int sl = qt + n_qt * k - n_qt;
-        const float mk = sm[sl][col][D];
-        const float ck = mt == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mk - mt);
-        l = fmaf(sm[sl][col][D + 1], ck, l);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) o[dt][i] = fmaf(sm[sl][col][dt * 16 + 4 * h4 + i], ck, o[dt][i]);
-      }
-      m = mt;
-    }
-  }
-  if (!vrow || ks != 0) return;
-  if (n_used == 1) {
-    const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-    __bf16* orow = a.out + (tok * a.H + head) * D + 4 * h4;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      bf16x4 v;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = static_cast<__bf16>(o[dt][i] * inv);
-      *reinterpret_cast<bf16x4*>(orow + dt * 16) = v;
-    }
-  } else {
-    float* pr = a.part + (static_cast<int64_t>(slot) * kGroupRows + qt * 16 + col) * LDSW;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-      *reinterpret_cast<f32x4*>(pr + dt * 16 + 4 * h4) = o[dt];
-    if (h4 == 0) {
-      pr[D] = m;
-      pr[D + 1] = l;
-    }
-  }
-}
-
 // Scoring chunks and prompt prefill (no plan, T > 1, >= 1024 cells): the workgroup's four
 // 16-row query tiles walk ONE key-block list — the agent's prefix blocks, then the history
 // blocks of every stream the 64 rows touch, up to the furthest query's causal limit — and
 // each 32-key block is staged through LDS once per workgroup (K rows padded to D + 8, V^T
 // rows to 40 keys: conflict-free fragment reads), double-buffered: the next block's 16-byte
-// global loads are in flight while the current one is attended from LDS.  The per-wave
-// kernel above loads every block once per tile (4x the L2 traffic for 64 rows of one
-// stream).  Blocks outside a tile's own stream or causal range are masked per lane, as
-// there; the arithmetic of a block is attend_block's, so the result matches the per-wave
-// kernel up to the order of the key blocks within a split (one split here).
+// global loads are in flight while the current one is attended from LDS (loading every
+// block once per tile instead is 4x the L2 traffic for 64 rows of one stream).  Blocks
+// outside a tile's own stream or causal range are masked per lane; the arithmetic of a
+// block is attend_block's.
 template <int D>
 struct LdsTile {
   static constexpr int KROW = D + 8;                 // bf16 per staged K row
@@ -442,11 +261,9 @@ struct LdsTile {
   static constexpr int NCH = D / 64;                 // 16-byte chunks per thread per operand
 };
 
-#ifndef CS_ATTN_LDS_W256
-#define CS_ATTN_LDS_W256 1   // waves per SIMD of the D = 256 variant (2: 208 B/lane of spills)
-#endif
+// D = 256: one wave per SIMD (two: 208 B/lane of spills)
 template <int D>
-__global__ __launch_bounds__(kAttnThreads, D <= 128 ? 2 : CS_ATTN_LDS_W256)
+__global__ __launch_bounds__(kAttnThreads, D <= 128 ? 2 : 1)
 void prefix_attn_lds_kernel(AttnParams a) {
   using LT = LdsTile<D>;
   constexpr int NDS = D / 32;
@@ -662,10 +479,9 @@ __device__ __forceinline__ void att_at(int i) {
 // Decode steps (a plan: few (group, head) cells, key splits): the agent's PREFIX blocks
 // are shared by the workgroup's four 16-row tiles, so the split's prefix blocks (split,
 // split + n_used, ...) are staged through LDS once per workgroup and attended by every
-// tile (the per-wave kernel loads each one per tile: 4x the load instructions, 68 % issue
-// stalls at C5); each tile's own streams' history blocks are then loaded per wave as
-// there.  Every key block is attended exactly once per (query row, split) as in the
-// per-wave assignment, so the split partials and the merge are unchanged.
+// tile (loading each one per tile: 4x the load instructions, 68 % issue stalls at C5);
+// each tile's own streams' history blocks are then loaded per wave (item_ref, load_block).
+// Every key block is attended exactly once per (query row, split).
 // two waves per SIMD at every D (D = 256: 237 VGPRs, no spills; 1 wave/SIMD before)
 //
 // ROWS (cs_prefix_attention_rows): the history is row-major for K AND V ([S][Hkv][ldh][D])
@@ -1234,33 +1050,6 @@ __global__ __launch_bounds__(256) void hist_rows_kernel(const int32_t* __restric
   dst[i] = j < *hist_base ? src[parent[s] * ldh + j] : static_cast<int32_t>(row_base + s);
 }
 
-// plan tunables (CS_ATTN_TARGET_WGS, CS_ATTN_MIN_ITEMS override; read once)
-int env_int(const char* name, int dflt, int lo, int hi) {
-  if (const char* e = getenv(name)) {
-    const int y = atoi(e);
-    if (y >= lo && y <= hi) return y;
-  }
-  return dflt;
-}
-int attn_target_wgs() {
-  static const int v = env_int("CS_ATTN_TARGET_WGS", kTargetWgsDefault, 1, 1 << 20);
-  return v;
-}
-// scoring chunks / prompt prefill on the LDS-staged kernel (CS_ATTN_LDS=0: the per-wave one)
-bool attn_lds() {
-  static const bool v = env_int("CS_ATTN_LDS", 1, 0, 1) != 0;
-  return v;
-}
-// decode steps (a plan): the prefix blocks through LDS (CS_ATTN_PLAN_LDS=0: per wave)
-bool attn_plan_lds() {
-  static const bool v = env_int("CS_ATTN_PLAN_LDS", 1, 0, 1) != 0;
-  return v;
-}
-int attn_min_items() {
-  static const int v = env_int("CS_ATTN_MIN_ITEMS", kMinItemsDefault, 1, 4096);
-  return v;
-}
-
 struct PlanCell {
   int32_t gi, qg, splits, per_wg;
 };
@@ -1326,7 +1115,7 @@ int64_t cs_prefix_attention_plan(const int32_t* prefix_len, int32_t n_prefix,
   }
   // one per-wave budget q for all cells (a cell of `items` blocks on kw waves takes
   // ceil(items / (q kw)) splits, at most kMaxSplit): the whole launch's wave-serial work
-  // spread over about attn_target_wgs() workgroups, never below attn_min_items() blocks per
+  // spread over about kPlanTargetWgs workgroups, never below kPlanMinItems blocks per
   // wave — so the split workgroups are about equally long and no cell is the long pole
   auto splits_of = [](const Cell& c, int64_t q) {
     return std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, (c.items + q * c.kw - 1) / (q * c.kw)));
@@ -1334,7 +1123,7 @@ int64_t cs_prefix_attention_plan(const int32_t* prefix_len, int32_t n_prefix,
   int64_t work = 0;
   for (const Cell& c : cl) work += (c.items + c.kw - 1) / c.kw;
   work *= Hkv;
-  const int64_t q = std::max<int64_t>(attn_min_items(), (work + attn_target_wgs() - 1) / attn_target_wgs());
+  const int64_t q = std::max<int64_t>(kPlanMinItems, (work + kPlanTargetWgs - 1) / kPlanTargetWgs);
   std::vector<PlanCell> cells;
   cells.reserve(cl.size());
   int64_t na = 0, nm = 0, slots = 0;
@@ -1462,14 +1251,10 @@ int prefix_attention_impl(const char* name, const void* q, const void* k_prefix,
   do {                                                                                  \
     if (hist_rows)                                                                      \
       hipLaunchKernelGGL((prefix_attn_plan_lds_kernel<DV, true>), grid, dim3(kAttnThreads), 0, st, a); \
-    else if (plan && attn_plan_lds())                                                        \
-      hipLaunchKernelGGL(prefix_attn_plan_lds_kernel<DV>, grid, dim3(kAttnThreads), 0, st, a); \
     else if (plan)                                                                      \
-      hipLaunchKernelGGL((prefix_attn_kernel<DV, true>), grid, dim3(kAttnThreads), 0, st, a); \
-    else if (attn_lds())                                                                \
-      hipLaunchKernelGGL(prefix_attn_lds_kernel<DV>, grid, dim3(kAttnThreads), 0, st, a); \
+      hipLaunchKernelGGL(prefix_attn_plan_lds_kernel<DV>, grid, dim3(kAttnThreads), 0, st, a); \
     else                                                                                \
-      hipLaunchKernelGGL((prefix_attn_kernel<DV, false>), grid, dim3(kAttnThreads), 0, st, a); \
+      hipLaunchKernelGGL(prefix_attn_lds_kernel<DV>, grid, dim3(kAttnThreads), 0, st, a); \
     if (plan)                                                                           \
       hipLaunchKernelGGL(attn_merge_kernel<DV>, merge_grid, dim3(kAttnThreads), 0, st, a); \
   } while (0)
@@ -1641,15 +1426,11 @@ int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t 
   r.D = D;
   if (D % 8 != 0 || D > 256) return fail(CS_ERR_INVALID, "cs_rope_place: head_dim must be a multiple of 8, <= 256");
   if (r.n_tok > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_rope_place: too many tokens");
-  // V by 32-slot tiles when the streams carry many tokens (CS_ROPE_VTILE=0: per token)
+  // V by 32-slot tiles when the streams carry many tokens
   const int64_t n_tiles = ld_hist / 32;
   const int64_t n_vwg = static_cast<int64_t>(n_groups) * n_str * Hkv * n_tiles;
-  {
-    static const bool vtile = env_int("CS_ROPE_VTILE", 1, 0, 1) != 0;   // read once
-    r.skip_v = (!part && !v_rows && T >= 32 && ld_hist % 32 == 0 && ld_qkv % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(qkv) % 16 == 0 && n_vwg <= 0x7fffffffLL &&
-                vtile) ? 1 : 0;
-  }
+  r.skip_v = (!part && !v_rows && T >= 32 && ld_hist % 32 == 0 && ld_qkv % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(qkv) % 16 == 0 && n_vwg <= 0x7fffffffLL) ? 1 : 0;
   // 8-pair (16-byte) items when every head's halves are 16-byte aligned, else 4-pair
   const bool p8 = part ? true
                        : (ld_qkv % 8 == 0 && reinterpret_cast<uintptr_t>(qkv) % 16 == 0 && D % 16 == 0);

@@ -287,7 +287,8 @@ __device__ __forceinline__ void beam_order(const BeamLds& L, uint32_t* Uw, int32
       sm_ord[r] = c;
     };
     if (BLOCK <= 256 && n_order <= kWaveBoundMaxK) {
-      // few kept beams (256-thread blocks): the wave bound instead of histogram passes
+      // few kept beams (cs_beam_select's 256-thread block): the wave bound instead of
+      // histogram passes (profiles/r01h_decode_tail_wave_bound.jsonl)
       __syncthreads();   // sm_n = 0 is visible before any append
       uint32_t lm = 0u;
 #pragma unroll
@@ -490,35 +491,19 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_step_kernel
   beam_tail<BLOCK>(L, Uw, wkey, W, A, C, kind, eps, n_order, n2, out_order, out_val, out_kept);
 }
 
-// wave-bound selection in the decode proposer (chunk and merge): every block shape
-// (CS_WB_ALL=1) or the 256-thread blocks with K <= 16 only (CS_WB_ALL=0)
-#ifndef CS_WB_ALL
-#define CS_WB_ALL 0
-#endif
-#define CS_WB_ON(BL, KK) \
-  (CS_WB_ALL ? wave_bound_ok<BL>(KK) : ((BL) <= 256 && (KK) <= kWaveBoundMaxK))
-#ifndef CS_PROP_PRIO
-#define CS_PROP_PRIO 2   // instruction-issue priority of the proposer waves
-#endif
-#ifndef CS_DECODE_KP1024
-#define CS_DECODE_KP1024 8   // proposer keys per lane in the 1024-thread fp32 blocks (4 or this)
-#endif
-#ifndef CS_DECODE_RAWKEYS
-#define CS_DECODE_RAWKEYS 1  // 16-bit logits: the proposer keeps the raw values, not 32-bit keys
-#endif
-#ifndef CS_DECODE_KP1024_RAW
-#define CS_DECODE_KP1024_RAW 16   // proposer elements per lane then (1024-thread blocks)
-#endif
-// elements per lane of a 1024-thread proposer chunk: 16-bit logits are held raw (two per
-// register) and their order keys recomputed on each pass, so twice the elements fit the
-// registers of the 32-bit keys -- half the proposer workgroups, and C3's whole grid
+// The decode launch: 1024-thread blocks, so split rows take four canonical splits per block
+// (split_partial) and the proposer keeps its 16 * 1024-element chunks (per-rank C3: 43.98 ->
+// 26.4 us, profiles/r05e_beam_ab_*.jsonl; 256-thread blocks measured slower at C1 too, 17.8 vs
+// 16.9 us, r05f_beam_ab.jsonl), 2 16-byte vectors in flight per lane in the agent rows.
+constexpr int kDecodeBlock = 1024;
+constexpr int kDecodeUnroll = 2;
+constexpr int kPropPrio = 2;   // instruction-issue priority of the proposer waves
+// elements per lane of a proposer chunk (8 32-bit keys for fp32): 16-bit logits are held raw
+// (two per register) and their order keys recomputed on each pass, so twice the elements fit
+// the registers of the 32-bit keys -- half the proposer workgroups, and C3's whole grid
 // (256 agent rows + 16 beams x 16 chunks) is resident in one round on 256 CUs
-constexpr int kp1024(int dtype) {
-  return (CS_DECODE_RAWKEYS && dtype != CS_F32) ? CS_DECODE_KP1024_RAW : CS_DECODE_KP1024;
-}
-#ifndef CS_DECODE_UN1024
-#define CS_DECODE_UN1024 2   // 16-byte vectors in flight per lane in the 1024-thread rows
-#endif
+// (profiles/r04b_decode_rawkeys_ab.jsonl)
+constexpr int kp1024(int dtype) { return dtype != CS_F32 ? 16 : 8; }
 // ---------------------------------------------------------------------------
 // beam decode step: proposer + scoring in ONE launch
 // ---------------------------------------------------------------------------
@@ -537,31 +522,20 @@ constexpr int kp1024(int dtype) {
 // Proposer blocks come first in the grid, so they are dispatched first.  No block waits
 // on another (last-arriver hand-offs only), so the launch cannot stall.  Bit-identical to
 // cs_vocab_topk + cs_beam_step (same selection, same lse arithmetic, same U formula).
-// Proposer keys per lane: the largest of 16 (256-thread blocks) or 8 (1024-thread blocks;
-// 16 would spill) that still gives >= 128 proposer workgroups, else 4 (few beams, e.g.
-// C5's B = 8), so the proposer finishes under the agent-row stream (tools/beam_ab.py
-// --sweep; profiles/r01f_beam_ab*.jsonl).  CS_DECODE_KP overrides (4, 8 or 16).
-int decode_kp(int32_t B, int64_t vocab, int32_t block, int32_t K, int dtype) {
-  const int big = block >= 1024 ? kp1024(dtype) : 16;
-  static const int env_kp = [] {       // read once
-    const char* e = getenv("CS_DECODE_KP");
-    return e ? atoi(e) : 0;
-  }();
-  if (env_kp == 4 || env_kp == big) return env_kp;
-  const int64_t nbig = B * ((vocab + big * block - 1) / (big * static_cast<int64_t>(block)));
-  const int64_t n4c = (vocab + 4LL * block - 1) / (4LL * block);
+// Proposer keys per lane: kp1024 (8 32-bit keys, 16 raw 16-bit values; more would spill) when
+// that still gives >= 128 proposer workgroups, else 4 (few beams, e.g. C5's B = 8), so the
+// proposer finishes under the agent-row stream (tools/beam_ab.py --sweep;
+// profiles/r01f_beam_ab*.jsonl).
+int decode_kp(int32_t B, int64_t vocab, int32_t K, int dtype) {
+  const int big = kp1024(dtype);
+  const int64_t nbig = B * ((vocab + big * kDecodeBlock - 1) / (big * static_cast<int64_t>(kDecodeBlock)));
+  const int64_t n4c = (vocab + 4LL * kDecodeBlock - 1) / (4LL * kDecodeBlock);
   return (nbig < 128 && n4c * K <= 16384) ? 4 : big;
 }
 // Grid order: the agent-row blocks first when they leave workgroup slots free for the
 // proposer (C3: 256 rows on 256 CUs x 2 slots), the proposer first when the rows alone
 // fill the chip (C5: 512 rows) — then the rows would starve the proposer to the end.
-// CS_DECODE_ROWS_FIRST=0/1 overrides.
-int decode_rows_first(int64_t row_blocks, int32_t block) {
-  static const int env_rf = [] {       // read once: -1 = not set
-    const char* e = getenv("CS_DECODE_ROWS_FIRST");
-    return e ? (atoi(e) == 1 ? 1 : 0) : -1;
-  }();
-  if (env_rf >= 0) return env_rf;
+int decode_rows_first(int64_t row_blocks) {
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0, v = 0;
@@ -571,7 +545,7 @@ int decode_rows_first(int64_t row_blocks, int32_t block) {
     else
       n_cu = 256;
   }
-  const int64_t slots = static_cast<int64_t>(n_cu) * (block >= 1024 ? 2 : 4);
+  const int64_t slots = static_cast<int64_t>(n_cu) * 2;   // 1024-thread workgroups per CU
   return row_blocks < slots ? 1 : 0;
 }
 #ifdef CS_TRACE_DECODE
@@ -640,7 +614,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
     // ---- proposer chunk ----
     // the proposer's short latency chain goes first when it shares a CU with a streaming
     // row block (instruction issue priority; the stream is bandwidth-bound, not issue-bound)
-    __builtin_amdgcn_s_setprio(CS_PROP_PRIO);
+    __builtin_amdgcn_s_setprio(kPropPrio);
     DEC_T(if (tid == 0) atomicMax(&g_dec_ts[1], q0);)
     constexpr int CH = KP * BLOCK;
     const int32_t b = pblk / nchunk_p;
@@ -652,7 +626,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
     // registers of 64-bit composite keys, so the 1024-thread variant does not spill.  RAW
     // (16-bit logits): the raw values instead, two per register, each pass recomputing the
     // identical key order_key(softcap(x)) from them (a few VALU ops per element per pass)
-    constexpr bool RAW = CS_DECODE_RAWKEYS && DT != CS_F32;
+    constexpr bool RAW = DT != CS_F32;
     constexpr int NWORD = RAW ? (KP + 1) / 2 : KP;
     uint32_t okey[NWORD];
     constexpr int EPV = Elt<DT>::kPerVec;
@@ -731,50 +705,25 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
     };
     if (tid == 0) sm_n = 0u;
     DEC_T(if (tid == 0) atomicMax(&g_dec_ts[10], wall_clock64());)
-    bool have = false;   // candidates collected (block-uniform)
-    // (256-thread variants only: in the 1024-thread ones the extra code's registers slow
-    // the agent-row stream more than the bound saves; profiles/r01h_decode_wave_bound.jsonl)
-    if (CS_WB_ON(BLOCK, K)) {
-      uint32_t lm = 0u;
-      fresh();
+    // radix select, no wave bound: in these 1024-thread blocks the bound's registers slow the
+    // agent-row stream more than the bound saves (profiles/r01h_decode_wave_bound.jsonl)
+    const RadixCut cut = radix_select<BLOCK>(
+        [&](auto f) {
+          fresh();
 #pragma unroll
-      for (int j = 0; j < KP; ++j)
-        if (local(j) < n) lm = max(lm, key32(j));
-      const uint32_t t = wave_bound<BLOCK>(lm, K, sm_tw);
-      fresh();
+          for (int j = 0; j < KP; ++j)
+            if (local(j) < n) f(key_of(j));
+        },
+        static_cast<uint32_t>(K), static_cast<uint32_t>(2 * K + 64), hist, sm_tw, sm_res);
+    fresh();
 #pragma unroll
-      for (int j = 0; j < KP; ++j) {
-        if (local(j) < n && key32(j) >= t) {
-          const uint32_t at = atomicAdd(&sm_n, 1u);
-          if (at < kTopkCand) sel_cand[at] = key_of(j);
-        }
-      }
-      __syncthreads();
-      have = sm_n <= static_cast<uint32_t>(kTopkCand);
-      if (!have) {   // massive ties at the bound: the radix path below
-        __syncthreads();
-        if (tid == 0) sm_n = 0u;
+    for (int j = 0; j < KP; ++j) {
+      if (local(j) < n) {
+        const unsigned long long kj = key_of(j);
+        if ((kj >> cut.shift) >= cut.prefix) sel_cand[atomicAdd(&sm_n, 1u)] = kj;
       }
     }
-    if (!have) {
-      const RadixCut cut = radix_select<BLOCK>(
-          [&](auto f) {
-            fresh();
-#pragma unroll
-            for (int j = 0; j < KP; ++j)
-              if (local(j) < n) f(key_of(j));
-          },
-          static_cast<uint32_t>(K), static_cast<uint32_t>(2 * K + 64), hist, sm_tw, sm_res);
-      fresh();
-#pragma unroll
-      for (int j = 0; j < KP; ++j) {
-        if (local(j) < n) {
-          const unsigned long long kj = key_of(j);
-          if ((kj >> cut.shift) >= cut.prefix) sel_cand[atomicAdd(&sm_n, 1u)] = kj;
-        }
-      }
-      __syncthreads();
-    }
+    __syncthreads();
     DEC_T(if (tid == 0) atomicMax(&g_dec_ts[11], wall_clock64());)
     const int32_t nkeys = nchunk_p * K;
     unsigned long long* pr = ppart + static_cast<int64_t>(b) * pad_line(nkeys, 8);
@@ -818,34 +767,12 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
         }
       }
     };
-    bool mhave = false;
-    if (CS_WB_ON(BLOCK, K) && cached) {
-      uint32_t lm = 0u;
-#pragma unroll
-      for (int r = 0; r < MR; ++r) lm = max(lm, static_cast<uint32_t>(mk[r] >> 32));
-      const uint32_t t = wave_bound<BLOCK>(lm, K, sm_tw);
-#pragma unroll
-      for (int r = 0; r < MR; ++r) {
-        if (mk[r] && static_cast<uint32_t>(mk[r] >> 32) >= t) {
-          const uint32_t at = atomicAdd(&sm_n, 1u);
-          if (at < kTopkCand) sel_cand[at] = mk[r];
-        }
-      }
-      __syncthreads();
-      mhave = sm_n <= static_cast<uint32_t>(kTopkCand);
-      if (!mhave) {
-        __syncthreads();
-        if (tid == 0) sm_n = 0u;
-      }
-    }
-    if (!mhave) {
-      const RadixCut mcut = radix_select<BLOCK>(
-          each_key, static_cast<uint32_t>(K), static_cast<uint32_t>(2 * K + 64), hist, sm_tw, sm_res);
-      each_key([&](unsigned long long c) {
-        if ((c >> mcut.shift) >= mcut.prefix) sel_cand[atomicAdd(&sm_n, 1u)] = c;
-      });
-      __syncthreads();
-    }
+    const RadixCut mcut = radix_select<BLOCK>(
+        each_key, static_cast<uint32_t>(K), static_cast<uint32_t>(2 * K + 64), hist, sm_tw, sm_res);
+    each_key([&](unsigned long long c) {
+      if ((c >> mcut.shift) >= mcut.prefix) sel_cand[atomicAdd(&sm_n, 1u)] = c;
+    });
+    __syncthreads();
     const int mc = static_cast<int>(sm_n);
     // the ids also stay in LDS: when this block gathers the beam it reads them there
     uint32_t* sm_ids = reinterpret_cast<uint32_t*>(sm_ord);
@@ -1098,7 +1025,6 @@ namespace {
 // counters][row lse][proposer chunk winners][split partials]
 struct DecodeLayout {
   SplitPlan plan;
-  int32_t block;
   int32_t kp;
   int32_t nchunk_p;
   size_t lse_off, ids_off, ppart_off, part_off, total;
@@ -1107,18 +1033,8 @@ DecodeLayout decode_layout(int32_t A, int32_t B, int64_t vocab, int32_t K, int d
   DecodeLayout d;
   const int64_t rows = static_cast<int64_t>(A) * B;
   d.plan = plan_split(rows, vocab, dtype);
-  // 1024-thread blocks: split rows take four canonical splits per block (split_partial), so
-  // the proposer keeps its 16 * 1024-element chunks (per-rank C3: 43.98 -> 26.4 us,
-  // profiles/r05e_beam_ab_*.jsonl).  256-thread blocks (one split each, wave-bound proposer
-  // selection for K <= 16) measured slower at C1 too: 17.8 vs 16.9 us (r05f_beam_ab.jsonl)
-  d.block = 1024;
-  static const int env_block = [] {    // A/B: 256 or 1024 whatever the split (read once)
-    const char* e = getenv("CS_DECODE_BLOCK");
-    return e ? atoi(e) : 0;
-  }();
-  if (env_block == 256 || env_block == 1024) d.block = env_block;
-  d.kp = decode_kp(B, vocab, d.block, K, dtype);
-  const int64_t ch = static_cast<int64_t>(d.kp) * d.block;
+  d.kp = decode_kp(B, vocab, K, dtype);
+  const int64_t ch = static_cast<int64_t>(d.kp) * kDecodeBlock;
   d.nchunk_p = static_cast<int32_t>((vocab + ch - 1) / ch);
   d.lse_off = kBeamCounterBytes + 2 * sizeof(uint32_t) * kBeamMaxBeams;
   d.ids_off = d.lse_off + sizeof(uint32_t) * static_cast<size_t>(B) * pad_line(A, 4);
@@ -1186,7 +1102,7 @@ int cs_beam_decode_step(const void* ref_logits, int64_t ld_ref, const void* logi
     return fail(CS_ERR_WORKSPACE, std::string(w) + "workspace smaller than cs_beam_decode_workspace_size()");
   if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
     return fail(CS_ERR_WORKSPACE, std::string(w) + "workspace not 8-byte aligned");
-  const int64_t row_blocks = rows * (d.plan.nsplit > 1 ? split_items(d.plan.nsplit, d.block) : 1);
+  const int64_t row_blocks = rows * (d.plan.nsplit > 1 ? split_items(d.plan.nsplit, kDecodeBlock) : 1);
   const int64_t grid = static_cast<int64_t>(B) * d.nchunk_p + row_blocks;
   if (grid > 0x7fffffffLL) return fail(CS_ERR_INVALID, std::string(w) + "grid too large");
   char* wsb = static_cast<char*>(workspace);
@@ -1208,26 +1124,22 @@ int cs_beam_decode_step(const void* ref_logits, int64_t ld_ref, const void* logi
   while (n2 < C) n2 <<= 1;
   const char* rg = static_cast<const char*>(ref_logits);
   const char* lg = static_cast<const char*>(logits);
-  const int32_t rows_first = decode_rows_first(row_blocks, d.block);
+  const int32_t rows_first = decode_rows_first(row_blocks);
   // 16-byte vector loads in the proposer when every reference row starts 16-B aligned
   const int32_t ref_vec = (reinterpret_cast<uintptr_t>(ref_logits) % 16 == 0 &&
                            (ld_ref * esz) % 16 == 0) ? 1 : 0;
-#define CS_DECODE_GO(DTV, CAPV, FIXV, BL, UN, KPV)                                                 \
-  hipLaunchKernelGGL((beam_decode_kernel<DTV, CAPV, FIXV, BL, UN, KPV>), dim3(grid), dim3(BL), 0,  \
+#define CS_DECODE_GO(DTV, CAPV, FIXV, KPV)                                                         \
+  hipLaunchKernelGGL((beam_decode_kernel<DTV, CAPV, FIXV, kDecodeBlock, kDecodeUnroll, KPV>),      \
+                     dim3(grid), dim3(kDecodeBlock), 0,                                            \
                      st, rg, ld_ref * esz, d.nchunk_p, rows_first, ref_vec, lg, vocab, ld * esz,   \
                      d.plan.nsplit, d.plan.split_len, A, B, K, rewards_in, softcap, inv_cap,       \
                      welfare_kind, static_cast<double>(eps), part, ppart, row_cnt, prop_cnt,       \
                      beam_cnt, done_cnt, wkey, lse_ws, ids_ws, out_ids, out_U, out_W, n_order, n2, \
                      out_order, out_order_val, out_kept)
-#define CS_DECODE_LAUNCH(DTV, CAPV, FIXV)                                                          \
-  do {                                                                                             \
-    if (d.block == 256) {                                                                          \
-      if (d.kp == 4) CS_DECODE_GO(DTV, CAPV, FIXV, 256, 8, 4);                                    \
-      else CS_DECODE_GO(DTV, CAPV, FIXV, 256, 8, 16);                                             \
-    } else {                                                                                       \
-      if (d.kp == 4) CS_DECODE_GO(DTV, CAPV, FIXV, 1024, CS_DECODE_UN1024, 4);                    \
-      else CS_DECODE_GO(DTV, CAPV, FIXV, 1024, CS_DECODE_UN1024, kp1024(DTV));                   \
-    }                                                                                              \
+#define CS_DECODE_LAUNCH(DTV, CAPV, FIXV)                        \
+  do {                                                           \
+    if (d.kp == 4) CS_DECODE_GO(DTV, CAPV, FIXV, 4);             \
+    else CS_DECODE_GO(DTV, CAPV, FIXV, kp1024(DTV));             \
   } while (0)
   if (dtype == CS_F32) {
     if (fixed) CS_DECODE_LAUNCH(CS_F32, true, true);

@@ -25,7 +25,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 
 #include "consensus_scoring.h"
@@ -501,23 +500,13 @@ struct SplitPlan {
   int64_t split_len;
 };
 
-inline int64_t target_wgs() {
-  // tuning knob (tools/beam_ab.py, split_sweep.py), read once per translation unit
-  static const int64_t v = [] {
-    const char* e = getenv("CS_TARGET_WGS");
-    const int64_t x = e ? atoll(e) : 0;
-    return x > 0 ? x : kTargetWgs;
-  }();
-  return v;
-}
-
-// Fewer rows than target_wgs(): split the vocabulary so that about target_wgs() x
-// kSplitQuad 256-thread split sub-blocks (target_wgs() 1024-thread workgroups of four) stream
+// Fewer rows than kTargetWgs: split the vocabulary so that about kTargetWgs x
+// kSplitQuad 256-thread split sub-blocks (kTargetWgs 1024-thread workgroups of four) stream
 // the rows -- each 1024-thread workgroup of the split kernels then has as many bytes in flight
 // as a whole unsplit row's workgroup.
 inline SplitPlan plan_split(int64_t rows, int64_t vocab, int dtype) {
   SplitPlan p{1, vocab};
-  const int64_t target = target_wgs();
+  const int64_t target = kTargetWgs;
   if (rows <= 0 || vocab <= 0 || rows >= target) return p;
   const int64_t grain = static_cast<int64_t>(kBlock) * elt_per_vec(dtype);  // one vector per lane
   const int64_t min_len = grain * kUnroll;  // >= one full unrolled sweep per split
@@ -735,9 +724,6 @@ __device__ __forceinline__ uint32_t wave_bound(uint32_t lane_max, int k, uint32_
   }
   return max(b1, b2);
 }
-// the bound needs ceil(k / NW) <= 64
-template <int BLOCK>
-__host__ __device__ constexpr bool wave_bound_ok(int k) { return k <= 64 * (BLOCK / 64); }
 constexpr int kWaveBoundMaxK = 16;   // larger k: radix_select (the bound passes too many)
 
 // ---------------------------------------------------------------------------

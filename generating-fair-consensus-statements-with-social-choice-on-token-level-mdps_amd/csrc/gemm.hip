@@ -372,18 +372,6 @@ __device__ __forceinline__ void ws2_accumulate(
     const int s = q / MT, i = q % MT;
     return *reinterpret_cast<const gbf16x8*>(base + x_swz(xr + 16 * i, s * 4 + (lane >> 4)));
   };
-#ifndef CS_WS2_THIN_RING
-// W steps in flight for row blocks of <= 80 rows: 6 measured 0-30 % SLOWER than 3 on every
-// per-rank / C1 shape (the longer prologue and tail outweigh the deeper stream;
-// profiles/r05s_gemm_{old,new}.jsonl), so 3
-#define CS_WS2_THIN_RING 3
-#endif
-#ifndef CS_GEMM_BIG_RING
-#define CS_GEMM_BIG_RING 0
-#endif
-#ifndef CS_GEMM_ASM_LDS
-#define CS_GEMM_ASM_LDS 6   // fragment reads in flight on the hand-counted path (0: off)
-#endif
   // this lane's B-fragment byte offset (row xr of tile 0, chunk s * 4 + lane / 16) inside a
   // stage: row tile i adds 16 * 128 B (the swizzle term (r >> 1) & 7 is the same for r and
   // r + 16 i), so one address per sub-step serves every row tile as an immediate offset
@@ -392,14 +380,14 @@ __device__ __forceinline__ void ws2_accumulate(
   const uint32_t fa1 = lds_u32 + x_swz(xr, 4 + (lane >> 4));
   auto compute = [&](int buf, const gbf16x8 (&w)[NT][2]) {
     const unsigned char* base = lds + buf * kStage;
-    if constexpr (CS_GEMM_ASM_LDS > 0 && MT > 9) {
+    if constexpr (MT > 9) {
       // hand-counted LDS pipeline for the large row counts (2 waves per SIMD): the fragment
       // reads are inline asm (invisible to the compiler's waitcnt pass, which otherwise
       // drains every read with lgkmcnt(0) before its first use), kR reads in flight; before
       // fragment q's MFMAs one counted lgkmcnt(n) names q's register as read-write, so its
       // MFMAs consume the landed value.  Measured 5-11 % faster at M = 272 / 520 and neutral
       // to 10 % slower at M <= 144 (profiles/r03g_gemm_asm_lds_ab.json), hence MT > 9 only.
-      constexpr int kR = CS_GEMM_ASM_LDS > 0 ? CS_GEMM_ASM_LDS : 1;
+      constexpr int kR = 6;   // fragment reads in flight
       const uint32_t a0 = fa0 + buf * kStage, a1 = fa1 + buf * kStage;
       gbf16x8 f[kR];
       auto rd = [a0, a1](gbf16x8 (&fr)[kR], auto qc) {
@@ -423,20 +411,11 @@ __device__ __forceinline__ void ws2_accumulate(
         for (int j = 0; j < NT; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[j][sub], v, acc[i][j], 0, 0, 0);
       });
-    } else if constexpr (MT > 9 && CS_GEMM_BIG_RING == 0) {   // 2 waves per SIMD, no registers left for a ring
-#pragma unroll
-      for (int q = 0; q < kQ; ++q) {
-        const gbf16x8 xf = frag(base, q);
-        const int s = q / MT, i = q % MT;
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[j][s], xf, acc[i][j], 0, 0, 0);
-      }
     } else {
       // B-fragments through a ring of kRing registers, kRing - 1 reads ahead of their
       // MFMAs; the schedule is pinned (ring fill, then one ds_read per NT MFMAs) so the LDS
       // round trip hides behind the MFMAs of earlier fragments
-      constexpr int kRing = MT > 9 ? (CS_GEMM_BIG_RING > 1 ? CS_GEMM_BIG_RING : 3) : 4;
+      constexpr int kRing = 4;
       gbf16x8 f[kRing];
 #pragma unroll
       for (int q = 0; q < kRing - 1; ++q) f[q] = frag(base, q);
@@ -484,11 +463,12 @@ __device__ __forceinline__ void ws2_accumulate(
   // the older W(t)) with the loads of steps t - 2 and t - 1 after it still in flight, passes
   // the barrier (every wave done with step t - 1, so buffer (t + 2) % 3 — read in step
   // t - 1 — is free), issues X(t + 2) into it, computes, then loads W(t + R) into the set
-  // it used: W (HBM) R steps ahead, X (L2) two.  R = 3 (CS_WS2_THIN_RING for the thin row
-  // blocks; the younger loads at step t's wait are the same W(t + R - 2), X(t + 1),
-  // W(t + R - 1) for every R, so kWait holds; R % 3 == 0 keeps every step's LDS buffer a
-  // constant)
-  constexpr int R = MT <= 5 ? CS_WS2_THIN_RING : 3;
+  // it used: W (HBM) R steps ahead, X (L2) two.  R = 3: 6 for the thin row blocks (<= 80
+  // rows) measured 0-30 % slower on every per-rank / C1 shape, the longer prologue and tail
+  // outweigh the deeper stream (profiles/r05s_gemm_{old,new}.jsonl).  The younger loads at
+  // step t's wait are the same W(t + R - 2), X(t + 1), W(t + R - 1) for every R, so kWait
+  // holds; R % 3 == 0 keeps every step's LDS buffer a constant
+  constexpr int R = 3;
   static_assert(R % 3 == 0 && R >= 3, "the W ring: a multiple of the 3 X buffers");
   gbf16x8 wr[R][NT][2];
   cs_static_for<R - 2>([&](auto rc) { load_w(wr[decltype(rc)::value], decltype(rc)::value); });
@@ -563,9 +543,6 @@ __device__ __forceinline__ void ws2_store(const gf32x4 (&acc)[MT][NT], uint16_t*
 // W goes to registers through inline-asm loads, so the compiler's waits never drain the
 // DMA queue: one counted s_waitcnt vmcnt per step (this step's X and W landed, the next
 // two steps' loads still in flight) + a raw s_barrier.
-#ifndef CS_WS2_GATED4
-#define CS_WS2_GATED4 1   // variant 3 gated: 4 waves x 32 W rows (64 features) per workgroup
-#endif
 template <int MT, int NT, int GATED, int WAVES, bool PACKED = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void ws2_gemm_kernel(
     const uint16_t* __restrict__ X, int64_t ldx, const uint16_t* __restrict__ W, int64_t ldw,
@@ -853,7 +830,7 @@ void dispatch_ws2(int mt, int blocks, hipStream_t st, const uint16_t* X, int64_t
 // 4 x 32; 4: as 2 with at most 9 row tiles (144 rows) per workgroup)
 int64_t variant_bn(int variant, int gated) {
   if (variant == 1) return 128;
-  if (variant == 3) return gated && !CS_WS2_GATED4 ? 256 : 128;
+  if (variant == 3) return 128;
   return 256;
 }
 
@@ -878,11 +855,8 @@ int64_t ws2_grid(int64_t cells, int64_t mblocks) {
 // the packed gated form at <= 80 rows (the per-rank decode steps) with 7 waves x 32 W rows
 // (112 features) per workgroup: the 70B gate|up (57,344 rows) is then 256 workgroups on
 // the 256 CUs instead of 224 (8 waves x 32 rows)
-#ifndef CS_WS2_GATED7
-#define CS_WS2_GATED7 1
-#endif
 bool ws2_gated7(int variant, int64_t M, int64_t N, int gated, bool packed) {
-  return CS_WS2_GATED7 && gated && packed && (variant == 2 || variant == 4) && M <= 80 &&
+  return gated && packed && (variant == 2 || variant == 4) && M <= 80 &&
          N % 224 == 0;
 }
 
@@ -890,7 +864,7 @@ int resolve_variant(int variant, int64_t N, int gated) {
   if (variant == 0) variant = 2;
   if (thin_variant(variant)) return variant;
   if ((variant == 2 || variant == 4) && N % 256) variant = gated ? 1 : 3;
-  if (variant == 3 && gated && (!CS_WS2_GATED4 || N % 128)) variant = 2;
+  if (variant == 3 && gated && N % 128) variant = 2;
   return variant;
 }
 

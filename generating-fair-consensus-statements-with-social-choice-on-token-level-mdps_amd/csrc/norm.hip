@@ -208,14 +208,6 @@ __global__ __launch_bounds__(kNormThreads) void gated_act_kernel(
   *reinterpret_cast<u16x8*>(out + r * ldo + j) = o;
 }
 
-bool norm_vpt_form() {
-  static const bool v = [] {
-    const char* e = getenv("CS_NORM_VPT");
-    return e && atoi(e) == 1;
-  }();
-  return v;
-}
-
 int add_rms_launch(const char* name, const void* a, int64_t lda, const void* b, int64_t ldb,
                    const float* bp, int splits, const void* b_weight, void* s_out, int64_t lds,
                    const void* weight, int64_t rows, int64_t d, float eps, int plus_one, void* y,
@@ -255,20 +247,8 @@ int add_rms_launch(const char* name, const void* a, int64_t lda, const void* b, 
     hipLaunchKernelGGL((add_rms_kernel<V, false, kMaxSplits, BL>), grid, dim3(BL), 0, st, A, lda, \
                        B, ldb, WB, S, lds, W, d, eps, plus_one, Y, ldy, bp, splits)
   // one vector per thread up to d = 8192 (the block size depends on d only, so a norm's
-  // rounding is the same at every row count).  CS_NORM_VPT=1 (A/B only): the round-4 form,
-  // 256 threads with up to 4 vectors each
-  if (norm_vpt_form()) {
-    if (nv <= 256) {
-      CS_ADD_RMS(1, 256);
-    } else if (nv <= 512) {
-      CS_ADD_RMS(2, 256);
-    } else if (nv <= 1024) {
-      CS_ADD_RMS(4, 256);
-    } else {
-      hipLaunchKernelGGL((add_rms_kernel<16, false>), grid, dim3(kNormThreads), 0, st, A, lda, B, ldb,
-                         WB, S, lds, W, d, eps, plus_one, Y, ldy, nullptr, 0);
-    }
-  } else if (nv <= 256) {
+  // rounding is the same at every row count)
+  if (nv <= 256) {
     CS_ADD_RMS(1, 256);
   } else if (nv <= 512) {
     CS_ADD_RMS(1, 512);

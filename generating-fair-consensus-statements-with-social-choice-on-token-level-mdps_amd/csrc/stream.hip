@@ -96,14 +96,10 @@ __global__ __launch_bounds__(kMergeBlock) void lsg_merge_kernel(
                    cap, inv_cap, DT, lane, kMergeBlock);
 }
 
-// Streaming-kernel configurations compiled into the library.  Variant 0 (default) is
-// shape-aware, from the in-process A/B on the bench's data (profiles/r01_lsg_variants.jsonl):
+// Streaming-kernel shapes, from the A/B on the bench's data (profiles/r01_lsg_variants.jsonl):
 //   single pass (rows >= 2048): 1024 threads x 2 vectors in flight  (C2: 7.25 TB/s, 90.6 %)
 //   split-V (fewer rows):        the canonical split arithmetic (split_partial, cs_kernels.cuh):
 //                                256-thread sub-blocks x 2 vectors, 4 splits per 1024 threads
-// CS_LSG_VARIANT=<n> (host environment, read per launch) forces one configuration for
-// A/B timing (tools/lsg_variants.py).  All variants compute the same values up to the
-// order of the fp32 partial merges inside a row (|diff| ~ 1e-6).
 template <int DT, bool CAP, int BLOCK, int UNROLL>
 void launch_stream(const void* logits, int64_t items, int64_t vocab, int64_t ld_bytes,
                    const SplitPlan& plan, const int32_t* tgt, int32_t k, float cap, float inv_cap,
@@ -124,72 +120,32 @@ void launch_stream(const void* logits, int64_t items, int64_t vocab, int64_t ld_
                        out_lse, part);
 }
 
-int lsg_variant() {
-  static const int v = [] {            // A/B knob (tools/lsg_variants.py), read once
-    const char* e = getenv("CS_LSG_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-
 template <int DT, bool CAP>
 void launch_lsg(const void* logits, int64_t rows, int64_t vocab, int64_t ld_bytes,
                 const SplitPlan& plan, const int32_t* tgt, int32_t k, float cap, float* out_tok,
                 float* out_lse, float2* part, hipStream_t st, bool finish = true) {
   const float inv_cap = CAP ? 1.0f / cap : 0.0f;
   const int64_t items = rows * plan.nsplit;
-  switch (lsg_variant()) {
-    case 1:  // 512 x 4
-      launch_stream<DT, CAP, 512, 4>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                     out_tok, out_lse, part, st);
-      break;
-    case 2:
-      launch_stream<DT, CAP, 1024, 1>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                      out_tok, out_lse, part, st);
-      break;
-    case 3:
-      launch_stream<DT, CAP, 1024, 2>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                      out_tok, out_lse, part, st);
-      break;
-    case 4:
-      launch_stream<DT, CAP, 256, 8>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                     out_tok, out_lse, part, st);
-      break;
-    case 5:
-      launch_stream<DT, CAP, kBlock, kUnroll>(logits, items, vocab, ld_bytes, plan, tgt, k, cap,
-                                              inv_cap, out_tok, out_lse, part, st);
-      break;
-    case 6:
-      launch_stream<DT, CAP, 1024, 4>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                      out_tok, out_lse, part, st);
-      break;
-    case 7:
-      launch_stream<DT, CAP, 512, 8>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                     out_tok, out_lse, part, st);
-      break;
-    default:
-      if (plan.nsplit == 1) {
-        launch_stream<DT, CAP, 1024, 2>(logits, items, vocab, ld_bytes, plan, tgt, k, cap,
-                                        inv_cap, out_tok, out_lse, part, st);
-      } else {
-        // the canonical split arithmetic, four splits per 1024-thread workgroup
-        const int64_t n_items = rows * split_items(plan.nsplit, 1024);
-        const char* lg = static_cast<const char*>(logits);
-        bool done = false;
-        if constexpr (CAP) {
-          if (fixed_lse_ok(cap)) {
-            hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, true, 1024>),
-                               dim3(static_cast<uint32_t>(n_items)), dim3(1024), 0, st, lg, n_items,
-                               vocab, ld_bytes, plan.nsplit, plan.split_len, cap, inv_cap, part);
-            done = true;
-          }
-        }
-        if (!done)
-          hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, false, 1024>),
-                             dim3(static_cast<uint32_t>(n_items)), dim3(1024), 0, st, lg, n_items,
-                             vocab, ld_bytes, plan.nsplit, plan.split_len, cap, inv_cap, part);
+  if (plan.nsplit == 1) {
+    launch_stream<DT, CAP, 1024, 2>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
+                                    out_tok, out_lse, part, st);
+  } else {
+    // the canonical split arithmetic, four splits per 1024-thread workgroup
+    const int64_t n_items = rows * split_items(plan.nsplit, 1024);
+    const char* lg = static_cast<const char*>(logits);
+    bool done = false;
+    if constexpr (CAP) {
+      if (fixed_lse_ok(cap)) {
+        hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, true, 1024>),
+                           dim3(static_cast<uint32_t>(n_items)), dim3(1024), 0, st, lg, n_items,
+                           vocab, ld_bytes, plan.nsplit, plan.split_len, cap, inv_cap, part);
+        done = true;
       }
-      break;
+    }
+    if (!done)
+      hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, false, 1024>),
+                         dim3(static_cast<uint32_t>(n_items)), dim3(1024), 0, st, lg, n_items,
+                         vocab, ld_bytes, plan.nsplit, plan.split_len, cap, inv_cap, part);
   }
   if (plan.nsplit > 1 && finish) {
     hipLaunchKernelGGL((lsg_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows)),

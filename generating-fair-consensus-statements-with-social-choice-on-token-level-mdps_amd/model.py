@@ -101,22 +101,14 @@ def rope_inv_freq(cfg: ModelConfig, device) -> torch.Tensor:
     return inv.to(torch.float32)
 
 
-# where a K-split projection's partials are folded in the stream forward: q|k|v inside
-# cs_rope_place_splitk (CS_FOLD_IN_ROPE=0: in cs_gemm_bf16's own launch); the output
-# projection inside the residual add's cs_add_rms_norm (CS_FOLD_IN_NORM=0: in its own
-# launch).  Round 4 measured the norm fold 0.4 ms slower at C5 (profiles/r04s_fold_ab.jsonl);
-# since round 5 it loads only its splits' partials, and round 6 measured it faster or equal
-# on every decode step: per-rank C3 5.76 -> 5.67 ms (with the per-rank output projection on
-# the packed K-split GEMM), per-rank C5 27.10 -> 26.94, one-GPU C5 76.4 -> 76.0, C1 / one-GPU
-# C3 within noise (profiles/r06v_fold_ab/)
-_FOLD_IN_ROPE = os.environ.get("CS_FOLD_IN_ROPE", "1") != "0"
-_PACK_LOCK = threading.Lock()
-_FOLD_IN_NORM = os.environ.get("CS_FOLD_IN_NORM", "1") != "0"
-# models without branch norms (Llama): an output or down projection that runs on hipBLASLt
-# (the scoring chunks, prompt prefill, C4's largest tree segments) adds into the residual in
+# Where a K-split projection's partials are folded in the stream forward: q|k|v inside
+# cs_rope_place_splitk, the output and down projections inside the residual add's
+# cs_add_rms_norm (faster or equal on every decode step: profiles/r06v_fold_ab/).  Models
+# without branch norms (Llama): an output or down projection that runs on hipBLASLt (the
+# scoring chunks, prompt prefill, C4's largest tree segments) adds into the residual in
 # hipBLASLt's epilogue (ops.linear_into_residual), and the residual add's launch only
-# normalises; the cs_gemm shapes keep their K-split fold in the residual add
-_RESID_IN_GEMM = os.environ.get("CS_RESID_IN_GEMM", "1") != "0"
+# normalises; the cs_gemm shapes keep their K-split fold in the residual add.
+_PACK_LOCK = threading.Lock()
 
 
 class Model:
@@ -529,7 +521,7 @@ class Model:
             # a K-split q|k|v (decode steps, T < 32) hands its partials to cs_rope_place, a
             # K-split output projection to the residual add: no fold launches
             qkv = ops.linear(x, self.wf[p + "qkv"], packed=wp.get(p + "qkv"),
-                             fold=T >= 32 or c.head_dim % 16 != 0 or not _FOLD_IN_ROPE)
+                             fold=T >= 32 or c.head_dim % 16 != 0)
             q = torch.empty(n_tok, H, D, dtype=h.dtype, device=h.device)
             kpl, vpl = hist_k[i], hist_vt[i]
             if hist_rows is not None and (hist_row_base or kpl.shape[0] != n_tok // T):
@@ -544,13 +536,13 @@ class Model:
                                      group_prefix=group_prefix,
                                      prefix_len_host=getattr(pfx, "lens_host", None),
                                      group_prefix_host=group_prefix_host, hist_rows=hist_rows)
-            resid = not g2 and _RESID_IN_GEMM
+            resid = not g2
             if resid and ops.linear_into_residual(o.view(n_tok, H * D), self.w[p + "wo"], h,
                                                   packed=wp.get(p + "wo")):
                 x = ops.add_rms_norm(h, self.w[p + "mlp_norm"], eps)
             else:
                 o = ops.linear(o.view(n_tok, H * D), self.w[p + "wo"], packed=wp.get(p + "wo"),
-                               fold=not _FOLD_IN_NORM)
+                               fold=False)
                 # Gemma-2's post-attention / post-MLP norms of the branch ride in the residual
                 # add's launch (b_weight): one cs_add_rms_norm per residual add
                 x = ops.add_rms_norm(h, self.w[p + "mlp_norm"], eps, b=o, s_out=h, plus_one=g2,

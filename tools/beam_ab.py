@@ -1,10 +1,6 @@
 #!/usr/bin/env python3
 """A/B timing of the beam-step pieces on resident logits (HIP events, GPU kept busy so the
-host never gaps the queue).  python tools/beam_ab.py [--only c3,c5] [--lib alt.so]
-
-The library reads its planning knobs (CS_DECODE_BLOCK, CS_DECODE_KP, CS_DECODE_ROWS_FIRST,
-CS_TARGET_WGS) once per process: sweep them by running this tool once per setting, e.g.
-CS_DECODE_KP=4 python tools/beam_ab.py --only c5."""
+host never gaps the queue).  python tools/beam_ab.py [--only c3,c5] [--lib alt.so]"""
 import importlib
 import json
 import os

@@ -3,7 +3,7 @@
 tokens, Llama-3.1-8B heads) and a decode step (C5: 520 streams x 1 token): HIP-event us per
 launch and the bytes it must move (qkv read + q / k / v written).
 
-    CS_ROPE_VTILE=0|1 python tools/rope_bench.py
+    python tools/rope_bench.py
 """
 import importlib
 import json
@@ -52,8 +52,8 @@ def run(name, reps=50):
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / reps
     nbytes = 2 * n * (H + 2 * Hkv) * D * 2
-    print(json.dumps({"shape": name, "vtile_env": os.environ.get("CS_ROPE_VTILE", "default"),
-                      "us": us, "bytes": nbytes, "gb_per_s": nbytes / us / 1e3}), flush=True)
+    print(json.dumps({"shape": name, "us": us, "bytes": nbytes, "gb_per_s": nbytes / us / 1e3}),
+          flush=True)
 
 
 if __name__ == "__main__":

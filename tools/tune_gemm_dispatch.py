@@ -32,11 +32,11 @@ model = importlib.import_module(PKG + ".model")
 # timed without cs_gemm_bf16's own fold
 FOLDED_BY_CONSUMER = ("qkv", "down")
 # the output projection's consumer is the residual add + RMSNorm, which folds its K-split
-# partials itself (model._FOLD_IN_NORM, the default since round 6): every form of it is
+# partials itself: every form of it is
 # timed TOGETHER with that cs_add_rms_norm launch (hipBLASLt / unsplit: the bf16 product
 # added; split: the partials folded in the norm), so the fold's bytes are priced where
 # they are read ("with_norm" in the record)
-WITH_NORM = ("o",) if model._FOLD_IN_NORM else ()
+WITH_NORM = ("o",)
 
 CONFIGS = {"c1": ("llama-3.2-1b", 4, 4), "c3": ("gemma-2-9b", 16, 16), "c5": ("llama-3.3-70b", 64, 8),
            "c4": ("llama-3.1-8b", 32, 0)}
