@@ -177,10 +177,12 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
     bi[d] = 0x7fffffff;
   }
   float m = -INFINITY, s = 0.0f;
+  bool saw_nan = false;
   for (int64_t v = v0 + tid; v < v1; v += 256) {
     float x = load_any<DT>(rp, v);
     if (CAP) x = softcap_fn(x, cap, inv_cap);
     const float y = x * inv_temp;
+    saw_nan |= y != y;
     lse_accum<1>(m, s, &y);
 #pragma unroll
     for (int d = 0; d < kMaxDraws; ++d) {
@@ -193,6 +195,13 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
         }
       }
     }
+  }
+  // lse_accum drops a NaN that arrives while (m, s) is still empty (fmaxf(-inf, NaN) is
+  // -inf), but a NaN token must poison the row's lse wherever it sits: (0, NaN) survives
+  // every merge, also with empty partners
+  if (saw_nan) {
+    if (m == -INFINITY) m = 0.0f;
+    s = __builtin_nanf("");
   }
   wave_lse_reduce(m, s);
 #pragma unroll
@@ -249,11 +258,17 @@ __global__ __launch_bounds__(64) void vocab_sample_merge_kernel(
       const DrawBest p = draw_part[(row * nsplit + j) * n_draw + d];
       draw_merge(b, i, p.s, p.idx);
     }
-    out_ids[row * n_draw + d] = i;
+    // no split offered a candidate (every logit -inf or NaN): id -1 and NaN, nothing read
+    const bool none = i == 0x7fffffff;
+    out_ids[row * n_draw + d] = none ? -1 : i;
     if (out_lp) {
-      float x = load_any<DT>(logits + row * ld_bytes, i);
-      if (CAP) x = softcap_fn(x, cap, inv_cap);
-      out_lp[row * n_draw + d] = x * inv_temp - lse;
+      float lp = __builtin_nanf("");
+      if (!none) {
+        float x = load_any<DT>(logits + row * ld_bytes, i);
+        if (CAP) x = softcap_fn(x, cap, inv_cap);
+        lp = x * inv_temp - lse;
+      }
+      out_lp[row * n_draw + d] = lp;
     }
   }
 }

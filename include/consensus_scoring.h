@@ -249,6 +249,10 @@ int cs_vocab_topk(const void* logits, int dtype, int64_t rows, int64_t vocab, in
  * documented in oracle/oracle.py (splitmix64 of (seed, v), top 23 bits + 0.5, scaled by 2^-23).
  * out_lp (nullable) receives the drawn token's log-probability under
  * softmax(x'/temperature).  n_draw <= 16.
+ * A token whose x' is -inf or NaN is never drawn; any NaN logit in the row makes the
+ * row's log-probabilities NaN.  A row with no finite logit yields id -1 and NaN, which
+ * callers must filter, like the NaN of an out-of-range target.  (What is judged is x':
+ * a soft-cap maps a -inf logit to -softcap, an ordinary token.)
  *
  * Replaces the remote one-token samplers: client.completions.create(max_tokens=1,
  * seed=base_seed+attempt, logit_bias) (src/methods/beam_search.py:253-297),

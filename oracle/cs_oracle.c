@@ -27,6 +27,11 @@
  *                             (Python sorted(reverse=True) stability,
  *                             beam_search.py:558-560; np.argmax first max,
  *                             best_of_n.py:198).
+ *   oracle_gumbel_sample      the product's seeded Gumbel-max draw (the contract of
+ *                             cs_vocab_sample in include/consensus_scoring.h, which replaces
+ *                             the remote one-token samplers of beam_search.py:253-297,
+ *                             finite_lookahead.py:310-334 and best_of_n.py:104-118), with
+ *                             each draw's runner-up gap, tie count and candidate margin.
  *
  * Row loops are OpenMP-parallel when built with -fopenmp (used only for the timed
  * CPU baseline; results do not depend on the thread count).
@@ -159,6 +164,117 @@ void oracle_welfare(const double* U, int32_t A, int32_t C, int64_t ldu, int kind
     }
     W[c] = any ? acc : NAN;
   }
+}
+
+/* The product's counter-based uniform (csrc/proposer.hip:cs_uniform): splitmix64 finaliser
+ * of (seed, token), top 23 bits + 0.5 over 2^23 -- exact in fp32, so exact here. */
+static double or_uniform(uint64_t seed, uint64_t v) {
+  uint64_t x = seed * 0x9E3779B97F4A7C15ull + (v + 1ull) * 0xD1B54A32D192ED03ull;
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return ((double)(uint32_t)(x >> 41) + 0.5) / 8388608.0;
+}
+
+/*
+ * Seeded Gumbel-max draws in fp64 (the contract of cs_vocab_sample, include/consensus_scoring.h):
+ * draw d of row r is argmax_v s[v], s[v] = y[v] + g(seeds[r*n_draw+d], v), y = cap(x) / T (the
+ * soft-cap applied before the division), g = -log(-log(u)); the lowest id wins an exact tie.
+ * A -inf or NaN token is never selected; a row with no selectable token gives id -1 and a NaN
+ * log-prob; any NaN in the row makes the row's log-probs NaN.
+ *
+ * Per draw: out_ids, out_lp (log softmax(y) at the id), out_gap = s[best] - s[runner-up] (+inf
+ * with fewer than two selectable tokens; 0 on an exact tie), out_ties = how many tokens hold
+ * exactly s[best], out_scale = max(1, max |y| over selectable tokens, max |g| over the row) --
+ * the magnitude an fp32 evaluation's rounding error scales with.  With cand_ids (nullable,
+ * [rows*n_draw]) out_cand_margin = s[best] - s[cand] (NaN when cand is not a selectable token).
+ */
+void oracle_gumbel_sample(const void* logits, int dtype, int64_t rows, int64_t vocab, int64_t ld,
+                          const uint64_t* seeds, int32_t n_draw, double temperature,
+                          double softcap, const int32_t* cand_ids, int32_t* out_ids,
+                          double* out_lp, double* out_gap, int32_t* out_ties, double* out_scale,
+                          double* out_cand_margin) {
+  const size_t es = elem_size(dtype);
+  double* lse = (double*)malloc(sizeof(double) * (size_t)(rows > 0 ? rows : 1));
+  double* ymax = (double*)malloc(sizeof(double) * (size_t)(rows > 0 ? rows : 1));
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+  for (int64_t r = 0; r < rows; ++r) {
+    const char* row = (const char*)logits + (size_t)r * (size_t)ld * es;
+    double mx = -INFINITY, amax = 0.0;
+    int has_nan = 0;
+    for (int64_t v = 0; v < vocab; ++v) {
+      const double y = cap_fn(load_elem(row, dtype, v), softcap) / temperature;
+      if (isnan(y)) has_nan = 1;
+      if (y > mx) mx = y;
+      if (isfinite(y) && fabs(y) > amax) amax = fabs(y);
+    }
+    double sum = 0.0;
+    for (int64_t v = 0; v < vocab; ++v) {
+      const double y = cap_fn(load_elem(row, dtype, v), softcap) / temperature;
+      if (!isnan(y)) sum += exp(y - mx);
+    }
+    lse[r] = has_nan ? NAN : mx + log(sum);
+    ymax[r] = amax;
+  }
+  const int64_t n = rows * (int64_t)n_draw;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+  for (int64_t rd = 0; rd < n; ++rd) {
+    const int64_t r = rd / n_draw;
+    const char* row = (const char*)logits + (size_t)r * (size_t)ld * es;
+    const uint64_t seed = seeds[rd];
+    double best = -INFINITY, second = -INFINITY, gmax = 0.0;
+    int64_t bi = -1;
+    int32_t ties = 0;
+    for (int64_t v = 0; v < vocab; ++v) {
+      const double g = -log(-log(or_uniform(seed, (uint64_t)v)));
+      if (fabs(g) > gmax) gmax = fabs(g);
+      const double y = cap_fn(load_elem(row, dtype, v), softcap) / temperature;
+      if (isnan(y) || y == -INFINITY) continue;
+      const double s = y + g;
+      if (bi < 0 || s > best) {       /* strictly greater: the lowest id keeps an exact tie */
+        second = bi < 0 ? -INFINITY : best;
+        best = s;
+        bi = v;
+        ties = 1;
+      } else if (s == best) {
+        second = best;
+        ++ties;
+      } else if (s > second) {
+        second = s;
+      }
+    }
+    out_ids[rd] = (int32_t)bi;
+    if (bi < 0) {
+      out_lp[rd] = NAN;
+      if (out_gap) out_gap[rd] = NAN;
+      if (out_ties) out_ties[rd] = 0;
+    } else {
+      out_lp[rd] = cap_fn(load_elem(row, dtype, bi), softcap) / temperature - lse[r];
+      if (out_gap) out_gap[rd] = second == -INFINITY ? INFINITY : best - second;
+      if (out_ties) out_ties[rd] = ties;
+    }
+    if (out_scale) {
+      double m = ymax[r] > gmax ? ymax[r] : gmax;
+      out_scale[rd] = m > 1.0 ? m : 1.0;
+    }
+    if (cand_ids && out_cand_margin) {
+      const int32_t c = cand_ids[rd];
+      double mg = NAN;
+      if (bi >= 0 && c >= 0 && c < vocab) {
+        const double y = cap_fn(load_elem(row, dtype, c), softcap) / temperature;
+        if (!isnan(y) && y != -INFINITY) mg = best - (y + -log(-log(or_uniform(seed, (uint64_t)c))));
+      }
+      out_cand_margin[rd] = mg;
+    }
+  }
+  free(lse);
+  free(ymax);
 }
 
 /* greater-than in the selection order: value desc (NaN last), index asc */

@@ -35,6 +35,7 @@ MIN, SUM, SUMLOG, MAX = 0, 1, 2, 3
 
 _dbl_p = ctypes.POINTER(ctypes.c_double)
 _i32_p = ctypes.POINTER(ctypes.c_int32)
+_u64_p = ctypes.POINTER(ctypes.c_uint64)
 
 
 def build() -> str:
@@ -63,6 +64,11 @@ def lib():
         L.oracle_topk.argtypes = [_dbl_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                   ctypes.c_int32, _i32_p]
         L.oracle_topk.restype = None
+        L.oracle_gumbel_sample.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _u64_p,
+            ctypes.c_int32, ctypes.c_double, ctypes.c_double, _i32_p, _i32_p, _dbl_p, _dbl_p,
+            _i32_p, _dbl_p, _dbl_p]
+        L.oracle_gumbel_sample.restype = None
         L.oracle_num_threads.restype = ctypes.c_int
         L.oracle_set_num_threads.argtypes = [ctypes.c_int]
         _lib = L
@@ -175,15 +181,79 @@ def cs_uniform(seed: int, v: np.ndarray) -> np.ndarray:
     return ((x >> np.uint64(41)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
 
 
-def gumbel_sample(logits_row: np.ndarray, seed: int, temperature: float = 1.0):
-    """argmax_v x[v]/T + g(seed, v), first index on ties; returns (id, log-prob of id)."""
-    x = np.asarray(logits_row, dtype=np.float64) / temperature
-    u = cs_uniform(seed, np.arange(x.shape[0])).astype(np.float64)
-    s = x - np.log(-np.log(u))
-    i = int(np.argmax(s))
-    mx = x.max()
-    lse = mx + np.log(np.exp(x - mx).sum())
-    return i, float(x[i] - lse)
+def gumbel_sample(logits_row: np.ndarray, seed: int, temperature: float = 1.0,
+                  softcap: float = 0.0, *, candidate: int | None = None, scores: bool = False):
+    """argmax_v x'[v]/T + g(seed, v), the lowest id on an exact tie; returns (id, log-prob of
+    id).  x' = softcap * tanh(x / softcap) when softcap > 0, applied in fp64 BEFORE the
+    division by the temperature (include/consensus_scoring.h: softmax(x'/temperature)).
+
+    A -inf or NaN token is never selected.  A row with no selectable token returns
+    (-1, NaN); any NaN in the row makes the log-prob NaN.
+    scores=True appends the full perturbed-score vector s (fp64, -inf where a token is not
+    selectable); candidate=<id> appends the margin s[best] - s[candidate] (NaN when the
+    candidate is not a selectable token, or no token is)."""
+    x = np.asarray(logits_row, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if softcap > 0.0:
+            x = softcap * np.tanh(x / softcap)
+        y = x / temperature
+        ok = ~np.isnan(y) & (y != -np.inf)
+        u = cs_uniform(seed, np.arange(y.shape[0])).astype(np.float64)
+        s = np.where(ok, y - np.log(-np.log(u)), -np.inf)
+        if not ok.any():
+            i, lp = -1, float("nan")
+        else:
+            i = int(np.argmax(s))               # first maximum: the lowest id
+            if np.isnan(y).any():
+                lp = float("nan")
+            else:
+                mx = y[ok].max()
+                lp = float(y[i] - (mx + np.log(np.exp(y[ok] - mx).sum())))
+        out = [i, lp]
+        if scores:
+            out.append(s)
+        if candidate is not None:
+            c = int(candidate)
+            good = i >= 0 and 0 <= c < y.shape[0] and bool(ok[c])
+            out.append(float(s[i] - s[c]) if good else float("nan"))
+    return tuple(out)
+
+
+def gumbel_sample_rows(logits: np.ndarray, seeds: np.ndarray, temperature: float = 1.0,
+                       softcap: float = 0.0, *, bf16: bool = False, vocab: int | None = None,
+                       candidates: np.ndarray | None = None):
+    """gumbel_sample for every (row, draw) of a 2-D logits array (row stride = shape[1]; bf16
+    rows as uint16 bit patterns) and seeds [rows, n_draw] (int64 or uint64 bit patterns), by
+    the C layer (OpenMP over the draws).  Returns a dict of [rows, n_draw] arrays:
+      id     the drawn token (-1: no selectable token)      lp    its log-prob
+      gap    s[best] - s[runner-up] (0 on an exact tie, +inf with one selectable token)
+      ties   how many tokens hold exactly s[best]
+      scale  max(1, max |x'/T|, max |g|): what an fp32 evaluation's rounding error scales with
+      margin (with candidates [rows, n_draw]) s[best] - s[candidate], NaN if not selectable."""
+    assert logits.ndim == 2 and logits.flags.c_contiguous
+    rows, ld = logits.shape
+    vocab = ld if vocab is None else vocab
+    seeds = np.ascontiguousarray(seeds).reshape(rows, -1)
+    seeds = np.ascontiguousarray(seeds.view(np.uint64) if seeds.dtype == np.int64
+                                 else seeds.astype(np.uint64))
+    n_draw = seeds.shape[1]
+    L = lib()
+    out = {"id": np.empty((rows, n_draw), dtype=np.int32),
+           "lp": np.empty((rows, n_draw), dtype=np.float64),
+           "gap": np.empty((rows, n_draw), dtype=np.float64),
+           "ties": np.empty((rows, n_draw), dtype=np.int32),
+           "scale": np.empty((rows, n_draw), dtype=np.float64)}
+    cand = None
+    if candidates is not None:
+        cand = np.ascontiguousarray(candidates, dtype=np.int32).reshape(rows, n_draw)
+        out["margin"] = np.empty((rows, n_draw), dtype=np.float64)
+    L.oracle_gumbel_sample(logits.ctypes.data, dtype_code(logits, bf16), rows, vocab, ld,
+                           _p(seeds, _u64_p), n_draw, float(temperature), float(softcap),
+                           _p(cand, _i32_p) if cand is not None else None, _p(out["id"], _i32_p),
+                           _p(out["lp"], _dbl_p), _p(out["gap"], _dbl_p), _p(out["ties"], _i32_p),
+                           _p(out["scale"], _dbl_p),
+                           _p(out["margin"], _dbl_p) if cand is not None else None)
+    return out
 
 
 def vocab_topk(logits: np.ndarray, k: int):

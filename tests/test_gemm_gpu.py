@@ -291,3 +291,130 @@ def test_every_dispatched_production_shape_matches_fp32_product(ops, dev, key):
         assert y.shape == ref.shape, name
         err = (y.float() - ref).abs()
         assert bool((err <= tol).all()), (name, float(err.max()), float(ref.abs().max()))
+
+
+# --- the residual add's three routes (model.py's forward picks one per row count) ------------
+# The smallest K-split entry of the committed table, and a row count the table does not hold
+# for the same N, K (so that shape stays on hipBLASLt).
+ROUTE_N, ROUTE_K = 2048, 8192
+ROUTE_SPLIT_M, ROUTE_BLASLT_M = 8, 16
+ROUTE_EPS = 1e-6
+
+
+def _route_inputs(dev, M):
+    g = torch.Generator(device="cpu").manual_seed(1000 + M)
+    x = torch.randn(M, ROUTE_K, generator=g).to(dev, torch.bfloat16)
+    w = (torch.randn(ROUTE_N, ROUTE_K, generator=g) * 0.02).to(dev, torch.bfloat16)
+    h = (torch.randn(M, ROUTE_N, generator=g) * 2).to(dev, torch.bfloat16)
+    wt = (torch.randn(ROUTE_N, generator=g) * 0.1 + 1.0).to(dev, torch.bfloat16)
+    return x, w, h, wt
+
+
+def _rms_norm64(s, wt):
+    R = torch.sqrt((s * s).mean(-1, keepdim=True) + ROUTE_EPS)
+    return s * wt.double() / R, R
+
+
+def _route_check(name, h_dev, x_dev, prod, h0, wt, rounds_product):
+    """h_dev, x_dev: a route's next residual stream and its normed rows.  Returns the largest
+    error / bound of h, of x against the fp64 chain, and of x against the fp64 norm of h_dev."""
+    s = h0.double() + prod
+    # h: the folded routes round the product to bf16 and then the sum, the epilogue route
+    # rounds once; each also gets the GEMM tests' accumulation term (_tol)
+    t = 2.0 ** -8 * ((prod.abs() if rounds_product else 0.0) + s.abs()) + 1e-3 * prod.abs().max()
+    eh = (h_dev.double() - s).abs()
+    assert bool((eh <= t).all()), (name, "h", float((eh / t).max()))
+    # x against the fp64 chain: y_i = s_i g_i / R with R = sqrt(mean(s^2) + eps).  For
+    # |dh_i| <= t_i the rms moves by at most rho = rms(t) (it is a norm), so the exact norm of
+    # h_dev is within E_i = |g_i| / (R - rho) * (t_i + |s_i| rho / R) of y_i; the kernel's bf16
+    # rounding of an fp32 result adds 2^-8 |y*| + 2^-20 rms(y*) (test_row_kernels_gpu.py).
+    y, R = _rms_norm64(s, wt)
+    rho = t.pow(2).mean(-1, keepdim=True).sqrt()
+    E = wt.double().abs() / (R - rho) * (t + s.abs() * rho / R)
+    rms_y = y.pow(2).mean(-1, keepdim=True).sqrt()
+    rms_E = E.pow(2).mean(-1, keepdim=True).sqrt()
+    tx = E + 2.0 ** -8 * (y.abs() + E) + 2.0 ** -20 * (rms_y + rms_E)
+    ex = (x_dev.double() - y).abs()
+    assert bool((ex <= tx).all()), (name, "x", float((ex / tx).max()))
+    # x against the fp64 norm of the route's own h: one bf16 rounding of an fp32 result
+    y_own, _ = _rms_norm64(h_dev.double(), wt)
+    t_own = 2.0 ** -8 * y_own.abs() + 2.0 ** -20 * y_own.pow(2).mean(-1, keepdim=True).sqrt()
+    e_own = (x_dev.double() - y_own).abs()
+    assert bool((e_own <= t_own).all()), (name, "x of own h", float((e_own / t_own).max()))
+    out = float((eh / t).max()), float((ex / tx).max()), float((e_own / t_own).max())
+    print(f"residual route {name}: max err / bound  h {out[0]:.3f}  x {out[1]:.3f}  "
+          f"x of own h {out[2]:.3f};  max|dh| {float(eh.max()):.4f}")
+    return out
+
+
+def _folded_routes(ops, x, w, h, wt):
+    """linear(fold=False) + add_rms_norm(b=partials, s_out=h) and linear + add_rms_norm(b=y,
+    s_out=h) -> ((h, x_normed, the unfolded branch), (h, x_normed, y))."""
+    h_p, h_f = h.clone(), h.clone()
+    p = ops.linear(x, w, fold=False)
+    x_p = ops.add_rms_norm(h_p, wt, ROUTE_EPS, b=p, s_out=h_p)
+    y = ops.linear(x, w)
+    x_f = ops.add_rms_norm(h_f, wt, ROUTE_EPS, b=y, s_out=h_f)
+    return (h_p, x_p, p), (h_f, x_f, y)
+
+
+def test_residual_add_routes_on_a_k_split_shape(ops, dev):
+    """A shape the table runs as a K-split cs_gemm_bf16: the partials folded inside the
+    residual add, and the GEMM's own fold followed by the add -- each against the fp64 chain,
+    and bitwise equal to each other.  The epilogue route refuses the shape."""
+    M = ROUTE_SPLIT_M
+    ch = ops.gemm_choice(M, ROUTE_N, ROUTE_K)
+    assert ch is not None and ch["splits"] > 1 and not ch["packed"]
+    x, w, h, wt = _route_inputs(dev, M)
+    prod = x.double() @ w.double().t()
+    (h_p, x_p, p), (h_f, x_f, y) = _folded_routes(ops, x, w, h, wt)
+    assert isinstance(p, ops.SplitPartials) and tuple(p.part.shape) == (ch["splits"], M, ROUTE_N)
+    assert not isinstance(y, ops.SplitPartials) and y.dtype == torch.bfloat16
+    _route_check("K-split, partials folded in the add", h_p, x_p, prod, h, wt, True)
+    _route_check("K-split, GEMM fold then add", h_f, x_f, prod, h, wt, True)
+    assert torch.equal(h_p, h_f) and torch.equal(x_p, x_f)
+    h_e = h.clone()
+    assert ops.linear_into_residual(x, w, h_e) is False        # a shape the table dispatches
+    assert torch.equal(h_e, h)
+
+
+def test_residual_add_routes_on_a_hipblaslt_shape(ops, dev):
+    """A row count the table does not hold: the hipBLASLt epilogue (h += x w^T, rounded once)
+    + the norm alone, against linear + the residual add (product rounded, then the sum)."""
+    M = ROUTE_BLASLT_M
+    assert ops.gemm_choice(M, ROUTE_N, ROUTE_K) is None
+    x, w, h, wt = _route_inputs(dev, M)
+    prod = x.double() @ w.double().t()
+    h_e = h.clone()
+    assert ops.linear_into_residual(x, w, h_e) is True
+    x_e = ops.add_rms_norm(h_e, wt, ROUTE_EPS)
+    _route_check("hipBLASLt epilogue", h_e, x_e, prod, h, wt, False)
+    (h_p, x_p, p), (h_f, x_f, y) = _folded_routes(ops, x, w, h, wt)
+    # no K split here: fold=False returns the bf16 product, the same route as linear
+    assert not isinstance(p, ops.SplitPartials) and torch.equal(p, y)
+    _route_check("hipBLASLt, linear then add", h_f, x_f, prod, h, wt, True)
+    assert torch.equal(h_p, h_f) and torch.equal(x_p, x_f)
+    d = (h_e.double() - h_f.double()).abs()
+    print(f"residual routes, epilogue vs linear + add: {int((d > 0).sum())} of {d.numel()} "
+          f"elements of h differ, max {float(d.max()):.4f}")
+
+
+def test_linear_into_residual_refusals_leave_h_untouched(ops, dev):
+    M = ROUTE_BLASLT_M
+    x, w, h, _ = _route_inputs(dev, M)
+
+    def refused(xx, hh):
+        before = hh.clone()
+        assert ops.linear_into_residual(xx, w, hh) is False
+        assert torch.equal(hh, before)
+
+    wide = torch.zeros(M, ROUTE_N + 8, device=dev, dtype=torch.bfloat16)
+    wide[:, :ROUTE_N] = h
+    refused(x, wide[:, :ROUTE_N])                                   # a non-contiguous h
+    refused(x, h.float())                                           # an fp32 h
+    refused(x, torch.ones(M, ROUTE_N + 128, device=dev, dtype=torch.bfloat16))   # shape mismatch
+    refused(x, torch.ones(M + 1, ROUTE_N, device=dev, dtype=torch.bfloat16))
+    x8, _, h8, _ = _route_inputs(dev, ROUTE_SPLIT_M)
+    refused(x8, h8)                                                 # a dispatched shape
+    ok = h.clone()
+    assert ops.linear_into_residual(x, w, ok) is True and not torch.equal(ok, h)

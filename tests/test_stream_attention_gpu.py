@@ -373,7 +373,11 @@ def test_add_rms_norm_matches_torch(ops, dev, plus_one, d, with_b):
     assert float(diff.max()) <= float(y_ref.float().abs().max()) * 2 ** -7
 
 
-@pytest.mark.parametrize("plus_one,d", [(True, 3584), (True, 256), (False, 2048), (True, 8192)])
+@pytest.mark.parametrize("plus_one,d", [(True, 3584), (True, 256), (False, 2048), (True, 8192),
+                                        # above 8192 the weights are no longer prefetched
+                                        # (16 vectors per thread): other code, same bits
+                                        (True, 8200), (False, 8200), (True, 16384),
+                                        (True, 32768), (False, 32768)])
 def test_add_rms_norm_branch_prenorm_is_the_two_launches(ops, dev, plus_one, d):
     """b_weight (Gemma-2's post-attention / post-MLP norm of the branch) inside the residual
     add's launch is bitwise the separate launch over the branch followed by the add + norm."""
