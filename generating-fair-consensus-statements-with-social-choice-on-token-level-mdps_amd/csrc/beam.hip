@@ -362,6 +362,152 @@ __device__ __forceinline__ void beam_order(const BeamLds& L, uint32_t* Uw, int32
   }
 }
 
+#ifdef CS_TRACE_DECODE
+// cs_beam_decode_step's phases, slots: 0 first block start (min), 1 last proposer chunk
+// start, 2 last proposer chunk published, 3 last proposer merge done, 4 last row block start,
+// 5 first row lse, 6 last row lse, 7 last beam gather done, 8 tail start, 9 tail end
+// (wall_clock64 ticks)
+__device__ unsigned long long g_dec_ts[16];
+#define DEC_T(...) __VA_ARGS__
+#else
+#define DEC_T(...)
+#endif
+
+// ---------------------------------------------------------------------------
+// what cs_beam_step's and cs_beam_decode_step's kernels share
+// ---------------------------------------------------------------------------
+// The LDS of a beam kernel, instantiated once per kernel as __shared__.  One pool: the bf16
+// soft-cap table while a row streams, the proposer's and the tail's buffers otherwise (keys2
+// directly after keys: the selection path uses the pair as one 16 KB histogram).  The pool
+// comes first, so the 16-byte alignment it needs pads nothing.
+template <int DT, bool CAP, bool FIXED, int BLOCK>
+struct BeamSmem {
+  static constexpr bool kTab = CapTable<DT, CAP, FIXED>::kOn;
+  static constexpr int kPoolTail = 2 * kFusedSort + kTopkCand + kFusedSort;  // u64 words
+  static constexpr int kPool = kTab && kCapTab / 2 > kPoolTail ? kCapTab / 2 : kPoolTail;
+  alignas(16) unsigned long long pool[kPool];
+  float sm_m[BLOCK / 64];
+  float sm_s[BLOCK / 64];
+  uint32_t sm_tw[2 * BLOCK / 64];
+  int sm_res[2];
+  uint32_t sm_n;
+  int sm_last;   // a last-arriver decision, broadcast to the block
+
+  __device__ __forceinline__ float* ctab() { return reinterpret_cast<float*>(pool); }
+  __device__ __forceinline__ BeamLds view() {
+    unsigned long long* sel_cand = pool + 2 * kFusedSort;
+    float* sm_w = reinterpret_cast<float*>(sel_cand + kTopkCand);
+    return BeamLds{pool, pool + kFusedSort, sel_cand, sm_w,
+                   reinterpret_cast<int32_t*>(sm_w + kFusedSort), sm_tw, sm_res, &sm_n};
+  }
+};
+
+// One work item (row, sitem) of the agent-row stream: the item's (m, s) partial in the
+// streaming arithmetic of cs_logsoftmax_gather (block_lse_partial; split rows the canonical
+// split form, split_partial, BLOCK / 256 splits per block), published; the row's last arriver
+// merges the row's partials in split order (one wave, lanes over splits: lsg_merge_kernel's
+// arithmetic) and leaves the row's arrival counter at zero.  Returns, block-uniformly, whether
+// this block finished the row; then `lse` holds the row's log-sum-exp in thread 0.
+template <int DT, bool CAP, bool FIXED, int BLOCK, int UNROLL>
+__device__ __forceinline__ bool beam_row_stream(BeamSmem<DT, CAP, FIXED, BLOCK>& S,
+                                                const char* __restrict__ rp, int32_t row,
+                                                int32_t sitem, int32_t nsplit, int64_t split_len,
+                                                int64_t vocab, float cap, float inv_cap,
+                                                unsigned long long* __restrict__ part,
+                                                uint32_t* __restrict__ row_cnt, float& lse) {
+  const int tid = threadIdx.x;
+  if constexpr (BeamSmem<DT, CAP, FIXED, BLOCK>::kTab) {
+    build_cap_table<BLOCK>(S.ctab(), cap, inv_cap);
+    __syncthreads();
+  }
+  int32_t split = 0;
+  bool valid = true;
+  const float2 ms =
+      nsplit > 1 ? split_partial<DT, CAP, FIXED, BLOCK, true>(rp, sitem, nsplit, split_len, vocab, cap,
+                                                        inv_cap, S.sm_m, S.sm_s, S.ctab(), split, valid)
+                 : block_lse_partial<DT, CAP, FIXED, BLOCK, UNROLL, true>(rp, 0, vocab, cap, inv_cap,
+                                                                    S.sm_m, S.sm_s, S.ctab());
+  if (nsplit <= 1) {
+    if (tid == 0) lse = ms.x + logf(ms.y);
+    return true;
+  }
+  unsigned long long* rpart = part + static_cast<int64_t>(row) * pad_line(nsplit, 8);
+  if (valid && tid % kSplitSub == 0) {
+    st_sc1(rpart + split, (static_cast<unsigned long long>(__float_as_uint(ms.y)) << 32) |
+                              __float_as_uint(ms.x));
+    wait_stores();
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t nv = static_cast<uint32_t>(split_count(sitem, nsplit, BLOCK));
+    S.sm_last = arrive(&row_cnt[row], nv) + nv == static_cast<uint32_t>(nsplit);
+  }
+  __syncthreads();
+  if (!S.sm_last) return false;  // block-uniform
+  if (tid < 64) {
+    float m = -INFINITY, s = 0.0f;
+    for (int j = tid; j < nsplit; j += 64) {
+      const unsigned long long p = ld_sc1(rpart + j);
+      lse_merge(m, s, __uint_as_float(static_cast<uint32_t>(p)),
+                __uint_as_float(static_cast<uint32_t>(p >> 32)));
+    }
+    wave_lse_reduce(m, s);
+    if (tid == 0) {
+      lse = m + logf(s);
+      st_sc1(row_cnt + row, 0u);
+    }
+  }
+  return true;
+}
+
+// Candidate token t's logit in the row at rp; ids outside [0, vocab) are padding (!ok).
+template <int DT>
+__device__ __forceinline__ float beam_candidate_logit(const char* __restrict__ rp, int32_t t,
+                                                      int64_t vocab, bool& ok) {
+  ok = t >= 0 && t < vocab;
+  return ok ? load_one<DT>(rp, t) : 0.0f;
+}
+
+// One (agent, candidate): u = r + (softcap(x) - lse), NaN for padding, published to U; MIN /
+// MAX welfare is order-free, so a finite u is folded into the candidate's welfare key here.
+template <bool CAP>
+__device__ __forceinline__ void beam_store_utility(uint32_t* u_at, uint32_t* wkey_at, bool ok, float x,
+                                                   float lse, float r, float cap, float inv_cap,
+                                                   int kind) {
+  float lp = __builtin_nanf("");
+  if (ok) {
+    if (CAP) x = softcap_fn(x, cap, inv_cap);
+    lp = x - lse;
+  }
+  const float u = r + lp;
+  st_sc1(u_at, __float_as_uint(u));
+  if ((kind == CS_WELFARE_MIN || kind == CS_WELFARE_MAX) && __builtin_isfinite(u))
+    __hip_atomic_fetch_max(wkey_at, welfare_key(u, kind == CS_WELFARE_MIN), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The end of a beam launch: this block's U values (and welfare keys) are published, and the
+// last of the n blocks that get here resets the counter and runs the tail.
+template <int BLOCK, typename Smem>
+__device__ __forceinline__ void beam_finish(Smem& S, uint32_t* done_cnt, uint32_t n, uint32_t* Uw,
+                                            uint32_t* wkey, float* __restrict__ W, int32_t A,
+                                            int32_t C, int kind, double eps, int32_t n_order,
+                                            int32_t n2, int32_t* __restrict__ out_order,
+                                            float* __restrict__ out_val,
+                                            float* __restrict__ out_kept) {
+  const int tid = threadIdx.x;
+  wait_stores();
+  __syncthreads();
+  DEC_T(if (tid == 0) atomicMax(&g_dec_ts[7], wall_clock64());)
+  if (tid == 0) S.sm_last = arrive(done_cnt) == n - 1u;
+  __syncthreads();
+  if (!S.sm_last) return;  // block-uniform
+  if (tid == 0) st_sc1(done_cnt, 0u);
+  DEC_T(if (tid == 0) g_dec_ts[8] = wall_clock64();)
+  beam_tail<BLOCK>(S.view(), Uw, wkey, W, A, C, kind, eps, n_order, n2, out_order, out_val, out_kept);
+  DEC_T(if (tid == 0) g_dec_ts[9] = wall_clock64();)
+}
+
 template <int DT, bool CAP, bool FIXED, int BLOCK, int UNROLL>
 __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_step_kernel(
     const char* __restrict__ logits, int64_t vocab, int64_t ld_bytes, int32_t nsplit,
@@ -371,27 +517,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_step_kernel
     uint32_t* __restrict__ done_cnt, uint32_t* __restrict__ wkey, float* __restrict__ U,
     float* __restrict__ W, int32_t n_order, int32_t n2, int32_t* __restrict__ out_order,
     float* __restrict__ out_val, float* __restrict__ out_kept) {
-  __shared__ float sm_m[BLOCK / 64];
-  __shared__ float sm_s[BLOCK / 64];
+  __shared__ BeamSmem<DT, CAP, FIXED, BLOCK> S;
   __shared__ float sm_lse;
-  __shared__ int sm_last;
-  // one LDS pool: the bf16 soft-cap table while a row streams, the proposer's and the
-  // tail's buffers otherwise (keys2 directly after keys: the selection path uses the pair
-  // as one 16 KB histogram)
-  constexpr bool TAB = CapTable<DT, CAP, FIXED>::kOn;
-  constexpr int kPoolTail = 2 * kFusedSort + kTopkCand + kFusedSort;  // u64 words
-  constexpr int kPool = TAB && kCapTab / 2 > kPoolTail ? kCapTab / 2 : kPoolTail;
-  __shared__ __attribute__((aligned(16))) unsigned long long pool[kPool];
-  unsigned long long* keys = pool;
-  unsigned long long* keys2 = keys + kFusedSort;
-  unsigned long long* sel_cand = pool + 2 * kFusedSort;
-  float* sm_w = reinterpret_cast<float*>(sel_cand + kTopkCand);
-  int32_t* sm_ord = reinterpret_cast<int32_t*>(sm_w + kFusedSort);
-  float* ctab = reinterpret_cast<float*>(pool);
-  __shared__ uint32_t sm_tw[2 * BLOCK / 64];
-  __shared__ int sm_res[2];
-  __shared__ uint32_t sm_n;
-  const BeamLds L{keys, keys2, sel_cand, sm_w, sm_ord, sm_tw, sm_res, &sm_n};
   const int tid = threadIdx.x;
   const int32_t rows = A * B;
   const int32_t C = B * K;
@@ -403,92 +530,32 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_step_kernel
   const int32_t bm = row - ag * B;
   const char* rp = logits + row * ld_bytes;
   uint32_t* Uw = reinterpret_cast<uint32_t*>(U);
-  const bool order_free = kind == CS_WELFARE_MIN || kind == CS_WELFARE_MAX;
-  const bool is_min = kind == CS_WELFARE_MIN;
   // the candidate ids and their logits are read now (used only at the row finish), so
   // the finisher's gather costs no memory round trip after the lse is known
-  const int32_t t_pre = (tid < K) ? tgt[bm * K + tid] : -1;
-  const bool ok = t_pre >= 0 && t_pre < vocab;
-  const float xg = ok ? load_one<DT>(rp, t_pre) : 0.0f;
+  bool ok;
+  const float xg = beam_candidate_logit<DT>(rp, (tid < K) ? tgt[bm * K + tid] : -1, vocab, ok);
 
-  // 1. stream
-  if constexpr (TAB) {
-    build_cap_table<BLOCK>(ctab, cap, inv_cap);
-    __syncthreads();
-  }
-  int32_t split = 0;
-  bool valid = true;
-  // split rows: the canonical split arithmetic (split_partial), BLOCK / 256 splits per block
-  const float2 ms =
-      nsplit > 1 ? split_partial<DT, CAP, FIXED, BLOCK, true>(rp, sitem, nsplit, split_len, vocab, cap,
-                                                        inv_cap, sm_m, sm_s, ctab, split, valid)
-                 : block_lse_partial<DT, CAP, FIXED, BLOCK, UNROLL, true>(rp, 0, vocab, cap, inv_cap,
-                                                                    sm_m, sm_s, ctab);
-
-  // 2. row finish by the row's last arriver
-  if (nsplit > 1) {
-    if (valid && tid % kSplitSub == 0) {
-      st_sc1(part + static_cast<int64_t>(row) * pad_line(nsplit, 8) + split,
-             (static_cast<unsigned long long>(__float_as_uint(ms.y)) << 32) |
-                              __float_as_uint(ms.x));
-      wait_stores();
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const uint32_t nv = static_cast<uint32_t>(split_count(sitem, nsplit, BLOCK));
-      sm_last = arrive(&row_cnt[row], nv) + nv == static_cast<uint32_t>(nsplit);
-    }
-    __syncthreads();
-    if (!sm_last) return;  // block-uniform
-    if (tid < 64) {
-      float m = -INFINITY, s = 0.0f;
-      for (int j = tid; j < nsplit; j += 64) {
-        const unsigned long long p = ld_sc1(part + static_cast<int64_t>(row) * pad_line(nsplit, 8) + j);
-        lse_merge(m, s, __uint_as_float(static_cast<uint32_t>(p)),
-                  __uint_as_float(static_cast<uint32_t>(p >> 32)));
-      }
-      wave_lse_reduce(m, s);
-      if (tid == 0) {
-        sm_lse = m + logf(s);
-        st_sc1(row_cnt + row, 0u);
-      }
-    }
-  } else if (tid == 0) {
-    sm_lse = ms.x + logf(ms.y);
-  }
-  {
-    __syncthreads();
-    const float r0 = R[row];
-    const float lse = sm_lse;
-    for (int32_t j = tid; j < K; j += BLOCK) {
-      float x = xg;
-      bool okj = ok;
-      if (j >= BLOCK) {  // K > BLOCK: the remaining ids the early read did not cover
-        const int32_t t = tgt[bm * K + j];
-        okj = t >= 0 && t < vocab;
-        if (okj) x = load_one<DT>(rp, t);
-      }
-      float lp = __builtin_nanf("");
-      if (okj) {
-        if (CAP) x = softcap_fn(x, cap, inv_cap);
-        lp = x - lse;
-      }
-      const float u = r0 + lp;
-      st_sc1(Uw + static_cast<int64_t>(ag) * C + bm * K + j, __float_as_uint(u));
-      if (order_free && __builtin_isfinite(u))
-        __hip_atomic_fetch_max(wkey + bm * K + j, welfare_key(u, is_min), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
+  // 1. stream, 2. row finish by the row's last arriver
+  float row_lse = 0.0f;
+  if (!beam_row_stream<DT, CAP, FIXED, BLOCK, UNROLL>(S, rp, row, sitem, nsplit, split_len, vocab, cap,
+                                                      inv_cap, part, row_cnt, row_lse))
+    return;  // block-uniform
+  if (tid == 0) sm_lse = row_lse;
+  __syncthreads();
+  const float r0 = R[row];
+  const float lse = sm_lse;
+  for (int32_t j = tid; j < K; j += BLOCK) {
+    float x = xg;
+    bool okj = ok;
+    // K > BLOCK: the remaining ids the early read did not cover
+    if (j >= BLOCK) x = beam_candidate_logit<DT>(rp, tgt[bm * K + j], vocab, okj);
+    beam_store_utility<CAP>(Uw + static_cast<int64_t>(ag) * C + bm * K + j, wkey + bm * K + j, okj, x,
+                            lse, r0, cap, inv_cap, kind);
   }
 
   // 3. welfare + order by the last row
-  wait_stores();
-  __syncthreads();
-  if (tid == 0) sm_last = arrive(done_cnt) == static_cast<uint32_t>(rows - 1);
-  __syncthreads();
-  if (!sm_last) return;  // block-uniform
-  if (tid == 0) st_sc1(done_cnt, 0u);
-  beam_tail<BLOCK>(L, Uw, wkey, W, A, C, kind, eps, n_order, n2, out_order, out_val, out_kept);
+  beam_finish<BLOCK>(S, done_cnt, static_cast<uint32_t>(rows), Uw, wkey, W, A, C, kind, eps, n_order, n2,
+                     out_order, out_val, out_kept);
 }
 
 // The decode launch: 1024-thread blocks, so split rows take four canonical splits per block
@@ -548,15 +615,6 @@ int decode_rows_first(int64_t row_blocks) {
   const int64_t slots = static_cast<int64_t>(n_cu) * 2;   // 1024-thread workgroups per CU
   return row_blocks < slots ? 1 : 0;
 }
-#ifdef CS_TRACE_DECODE
-// slots: 0 first block start (min), 1 last proposer chunk start, 2 last proposer chunk
-// published, 3 last proposer merge done, 4 last row block start, 5 first row lse,
-// 6 last row lse, 7 last beam gather done, 8 tail start, 9 tail end (wall_clock64 ticks)
-__device__ unsigned long long g_dec_ts[16];
-#define DEC_T(...) __VA_ARGS__
-#else
-#define DEC_T(...)
-#endif
 constexpr int kBeamMaxBeams = 4096;
 
 template <int DT, bool CAP, bool FIXED, int BLOCK, int UNROLL, int KP>
@@ -572,33 +630,18 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
     uint32_t* __restrict__ ids_ws, int32_t* __restrict__ out_ids, float* __restrict__ U, float* __restrict__ W, int32_t n_order,
     int32_t n2, int32_t* __restrict__ out_order, float* __restrict__ out_val,
     float* __restrict__ out_kept) {
-  __shared__ float sm_m[BLOCK / 64];
-  __shared__ float sm_s[BLOCK / 64];
-  __shared__ float sm_lse;
-  __shared__ int sm_last;
-  // one LDS pool: the bf16 soft-cap table while a row streams, the proposer's and the
-  // tail's buffers otherwise (keys2 directly after keys: the selection path uses the pair
-  // as one 16 KB histogram)
-  constexpr bool TAB = CapTable<DT, CAP, FIXED>::kOn;
-  constexpr int kPoolTail = 2 * kFusedSort + kTopkCand + kFusedSort;  // u64 words
-  constexpr int kPool = TAB && kCapTab / 2 > kPoolTail ? kCapTab / 2 : kPoolTail;
-  __shared__ __attribute__((aligned(16))) unsigned long long pool[kPool];
-  unsigned long long* keys = pool;
-  unsigned long long* keys2 = keys + kFusedSort;
-  unsigned long long* sel_cand = pool + 2 * kFusedSort;
-  float* sm_w = reinterpret_cast<float*>(sel_cand + kTopkCand);
-  int32_t* sm_ord = reinterpret_cast<int32_t*>(sm_w + kFusedSort);
-  float* ctab = reinterpret_cast<float*>(pool);
-  __shared__ uint32_t sm_tw[2 * BLOCK / 64];
-  __shared__ int sm_res[2];
-  __shared__ uint32_t sm_n;
-  const BeamLds L{keys, keys2, sel_cand, sm_w, sm_ord, sm_tw, sm_res, &sm_n};
-  uint32_t* hist = reinterpret_cast<uint32_t*>(keys);  // 16 KB
+  __shared__ BeamSmem<DT, CAP, FIXED, BLOCK> S;
+  // the proposer's names for its part of the LDS
+  unsigned long long* sel_cand = S.view().sel_cand;
+  int32_t* sm_ord = S.view().sm_ord;
+  uint32_t* sm_tw = S.sm_tw;
+  int* sm_res = S.sm_res;
+  uint32_t& sm_n = S.sm_n;
+  int& sm_last = S.sm_last;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(S.pool);  // keys + keys2: 16 KB
   const int tid = threadIdx.x;
   const int32_t C = B * K;
   const int32_t n_prop = B * nchunk_p;
-  const bool is_min = kind == CS_WELFARE_MIN;
-  const bool order_free = kind == CS_WELFARE_MIN || kind == CS_WELFARE_MAX;
   uint32_t* Uw = reinterpret_cast<uint32_t*>(U);
   DEC_T(const unsigned long long q0 = wall_clock64(); if (tid == 0) atomicMin(&g_dec_ts[0], q0);)
   int32_t gb;  // the beam this block arrives at
@@ -796,51 +839,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
     const int32_t per_row = nsplit > 1 ? split_items(nsplit, BLOCK) : 1;
     const int32_t row = static_cast<int32_t>(item / per_row);
     const int32_t sitem = static_cast<int32_t>(item - static_cast<int64_t>(row) * per_row);
-    const char* rp = logits + row * ld_bytes;
-    if constexpr (TAB) {
-      build_cap_table<BLOCK>(ctab, cap, inv_cap);
-      __syncthreads();
-    }
-    int32_t split = 0;
-    bool valid = true;
-    // split rows: the canonical split arithmetic of cs_logsoftmax_gather / cs_beam_step
-    // (split_partial), so a 1024-thread launch (proposer chunks of 16 * 1024 elements) takes
-    // split rows four splits per block with the same bits as 256-thread splits
-    const float2 ms =
-        nsplit > 1 ? split_partial<DT, CAP, FIXED, BLOCK, true>(rp, sitem, nsplit, split_len, vocab, cap,
-                                                          inv_cap, sm_m, sm_s, ctab, split, valid)
-                   : block_lse_partial<DT, CAP, FIXED, BLOCK, UNROLL, true>(rp, 0, vocab, cap, inv_cap,
-                                                                      sm_m, sm_s, ctab);
-    if (nsplit > 1) {
-      if (valid && tid % kSplitSub == 0) {
-        st_sc1(part + static_cast<int64_t>(row) * pad_line(nsplit, 8) + split,
-               (static_cast<unsigned long long>(__float_as_uint(ms.y)) << 32) |
-                                __float_as_uint(ms.x));
-        wait_stores();
-      }
-      __syncthreads();
-      if (tid == 0) {
-        const uint32_t nv = static_cast<uint32_t>(split_count(sitem, nsplit, BLOCK));
-        sm_last = arrive(&row_cnt[row], nv) + nv == static_cast<uint32_t>(nsplit);
-      }
-      __syncthreads();
-      if (!sm_last) return;  // block-uniform
-      if (tid < 64) {
-        float m = -INFINITY, sum = 0.0f;
-        for (int j = tid; j < nsplit; j += 64) {
-          const unsigned long long pv = ld_sc1(part + static_cast<int64_t>(row) * pad_line(nsplit, 8) + j);
-          lse_merge(m, sum, __uint_as_float(static_cast<uint32_t>(pv)),
-                    __uint_as_float(static_cast<uint32_t>(pv >> 32)));
-        }
-        wave_lse_reduce(m, sum);
-        if (tid == 0) {
-          st_sc1(lse_ws + (row % B) * pad_line(A, 4) + row / B, __float_as_uint(m + logf(sum)));
-          st_sc1(row_cnt + row, 0u);
-        }
-      }
-    } else if (tid == 0) {
-      st_sc1(lse_ws + (row % B) * pad_line(A, 4) + row / B, __float_as_uint(ms.x + logf(ms.y)));
-    }
+    // the beam step's stream (the same bits: a 1024-thread launch, proposer chunks of 16 * 1024
+    // elements, takes split rows four splits per block); the row's finisher publishes its lse
+    float row_lse = 0.0f;
+    if (!beam_row_stream<DT, CAP, FIXED, BLOCK, UNROLL>(S, logits + row * ld_bytes, row, sitem, nsplit,
+                                                        split_len, vocab, cap, inv_cap, part, row_cnt,
+                                                        row_lse))
+      return;  // block-uniform
+    if (tid == 0) st_sc1(lse_ws + (row % B) * pad_line(A, 4) + row / B, __float_as_uint(row_lse));
     gb = row % B;
     DEC_T(if (tid == 0) { const unsigned long long q = wall_clock64(); atomicMax(&g_dec_ts[4], q0);
                           atomicMin(&g_dec_ts[5], q); atomicMax(&g_dec_ts[6], q); })
@@ -860,28 +866,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK >= 1024 ? 8 : 4) void beam_decode_kern
     const int32_t t = static_cast<int32_t>(ids_in_lds ? reinterpret_cast<const uint32_t*>(sm_ord)[j]
                                                       : ld_sc1(ids_ws + gb * pad_line(K, 4) + j));
     const float lse = __uint_as_float(ld_sc1(lse_ws + gb * pad_line(A, 4) + a));
-    float lp = __builtin_nanf("");
-    if (t >= 0 && t < vocab) {
-      float x = load_one<DT>(logits + row * ld_bytes, t);
-      if (CAP) x = softcap_fn(x, cap, inv_cap);
-      lp = x - lse;
-    }
-    const float u = R[row] + lp;
-    st_sc1(Uw + static_cast<int64_t>(a) * C + gb * K + j, __float_as_uint(u));
-    if (order_free && __builtin_isfinite(u))
-      __hip_atomic_fetch_max(wkey + gb * K + j, welfare_key(u, is_min), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+    bool ok;
+    const float x = beam_candidate_logit<DT>(logits + row * ld_bytes, t, vocab, ok);
+    beam_store_utility<CAP>(Uw + static_cast<int64_t>(a) * C + gb * K + j, wkey + gb * K + j, ok, x, lse,
+                            R[row], cap, inv_cap, kind);
   }
-  wait_stores();
-  __syncthreads();
-  DEC_T(if (tid == 0) atomicMax(&g_dec_ts[7], wall_clock64());)
-  if (tid == 0) sm_last = arrive(done_cnt) == static_cast<uint32_t>(B - 1);
-  __syncthreads();
-  if (!sm_last) return;  // block-uniform
-  if (tid == 0) st_sc1(done_cnt, 0u);
-  DEC_T(if (tid == 0) g_dec_ts[8] = wall_clock64();)
-  beam_tail<BLOCK>(L, Uw, wkey, W, A, C, kind, eps, n_order, n2, out_order, out_val, out_kept);
-  DEC_T(if (tid == 0) g_dec_ts[9] = wall_clock64();)
+  beam_finish<BLOCK>(S, done_cnt, static_cast<uint32_t>(B), Uw, wkey, W, A, C, kind, eps, n_order, n2,
+                     out_order, out_val, out_kept);
 }
 
 }  // namespace
@@ -913,6 +904,40 @@ __global__ __launch_bounds__(kSelectBlock) void beam_select_kernel(
 }
 }  // namespace
 
+namespace {
+// The limits cs_beam_step and cs_beam_decode_step share (rows = A * B, C = B * K).
+int check_beam_args(const char* fn, int64_t rows, int64_t C, int32_t n_order, const float* out_kept,
+                    int welfare_kind, float softcap) {
+  const std::string w = std::string(fn) + ": ";
+  if (C > kBeamMaxCand) return fail(CS_ERR_INVALID, w + "B*K exceeds 16384");
+  if (rows > kBeamMaxRows) return fail(CS_ERR_INVALID, w + "A*B exceeds 65536");
+  if (n_order < 0 || n_order > C) return fail(CS_ERR_INVALID, w + "need 0 <= n_order <= B*K");
+  if (out_kept && (n_order == 0 || C > kFusedSort))
+    return fail(CS_ERR_INVALID, w + "out_kept needs n_order > 0 and B*K <= 1024");
+  if (welfare_kind < CS_WELFARE_MIN || welfare_kind > CS_WELFARE_MAX)
+    return fail(CS_ERR_INVALID, w + "unknown welfare kind");
+  return check_softcap(fn, softcap);
+}
+
+// the head of both workspaces: [done counter | pad to 64 B][row counters][welfare keys]
+struct BeamCounters {
+  uint32_t *done_cnt, *row_cnt, *wkey;
+};
+BeamCounters beam_counters(char* wsb) {
+  return {reinterpret_cast<uint32_t*>(wsb), reinterpret_cast<uint32_t*>(wsb + kBeamRowCntOff),
+          reinterpret_cast<uint32_t*>(wsb + kBeamKeyOff)};
+}
+
+// More candidates than the launch sorts (n2 > kFusedSort): the launch wrote W, the order
+// comes from cs_segmented_topk's kernel behind it.
+void beam_sort_after(hipStream_t st, const float* W, int64_t C, int32_t n2, int32_t n_order,
+                     int32_t* out_order, float* out_order_val) {
+  if (n_order > 0 && n2 > kFusedSort)
+    hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(256), static_cast<size_t>(n2) * sizeof(unsigned long long),
+                       st, W, static_cast<int32_t>(C), C, n2, n_order, out_order, out_order_val);
+}
+}  // namespace
+
 extern "C" {
 
 int cs_beam_select(const float* W, int32_t C, int unfill, const float* U, int32_t A,
@@ -926,8 +951,7 @@ int cs_beam_select(const float* W, int32_t C, int unfill, const float* U, int32_
   if (A < 0) return fail(CS_ERR_INVALID, std::string(w) + "need A >= 0");
   if (!W || !out_order || (out_kept && A > 0 && !U))
     return fail(CS_ERR_INVALID, std::string(w) + "NULL pointer");
-  int32_t n2 = 2;
-  while (n2 < C) n2 <<= 1;
+  const int32_t n2 = next_pow2(C);
   hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(kSelectBlock), 0,
                      static_cast<hipStream_t>(stream), W, C, unfill,
                      reinterpret_cast<uint32_t*>(const_cast<float*>(U)), out_kept ? A : 0, out_W,
@@ -948,75 +972,42 @@ int cs_beam_step(const void* logits, int dtype, int32_t A, int32_t B, int64_t vo
                  int welfare_kind, float eps, float* out_U, float* out_W, int32_t n_order,
                  int32_t* out_order, float* out_order_val, float* out_kept, void* workspace,
                  size_t workspace_bytes, cs_stream_t stream) {
-  if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)
-    return fail(CS_ERR_INVALID, "cs_beam_step: unknown dtype");
-  if (A < 0 || B < 0 || K < 0 || vocab <= 0 || ld < vocab)
-    return fail(CS_ERR_INVALID, "cs_beam_step: need A, B, K >= 0, vocab > 0, ld >= vocab");
+  const char* fn = "cs_beam_step";
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (A < 0 || B < 0 || K < 0) return fail(CS_ERR_INVALID, std::string(fn) + ": need A, B, K >= 0");
   const int64_t rows = static_cast<int64_t>(A) * B;
   const int64_t C = static_cast<int64_t>(B) * K;
-  if (C > 16384) return fail(CS_ERR_INVALID, "cs_beam_step: B*K exceeds 16384");
-  if (rows > kBeamMaxRows) return fail(CS_ERR_INVALID, "cs_beam_step: A*B exceeds 65536");
-  if (n_order < 0 || n_order > C) return fail(CS_ERR_INVALID, "cs_beam_step: need 0 <= n_order <= B*K");
-  if (out_kept && (n_order == 0 || C > kFusedSort))
-    return fail(CS_ERR_INVALID, "cs_beam_step: out_kept needs n_order > 0 and B*K <= 1024");
-  if (welfare_kind < CS_WELFARE_MIN || welfare_kind > CS_WELFARE_MAX)
-    return fail(CS_ERR_INVALID, "cs_beam_step: unknown welfare kind");
-  if (!(softcap >= 0.0f) || std::isinf(softcap))
-    return fail(CS_ERR_INVALID, "cs_beam_step: softcap must be finite and >= 0");
+  if (int rc = check_beam_args(fn, rows, C, n_order, out_kept, welfare_kind, softcap)) return rc;
   if (C == 0) return CS_OK;
-  if (A == 0) return fail(CS_ERR_INVALID, "cs_beam_step: no agents");
+  if (A == 0) return fail(CS_ERR_INVALID, std::string(fn) + ": no agents");
   if (!logits || !targets || !rewards_in || !out_U || !out_W || (n_order > 0 && !out_order))
-    return fail(CS_ERR_INVALID, "cs_beam_step: NULL pointer");
-  if (reinterpret_cast<uintptr_t>(logits) % elt_size(dtype) != 0)
-    return fail(CS_ERR_INVALID, "cs_beam_step: logits not element-aligned");
+    return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
+  if (int rc = check_elt_aligned(fn, logits, dtype)) return rc;
   const SplitPlan plan = plan_split(rows, vocab, dtype);
   const size_t need = kBeamCounterBytes + static_cast<size_t>(rows) * pad_line(plan.nsplit, 8) *
                                               sizeof(unsigned long long);
-  if (!workspace || workspace_bytes < need)
-    return fail(CS_ERR_WORKSPACE, "cs_beam_step: workspace smaller than cs_beam_step_workspace_size()");
-  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return fail(CS_ERR_WORKSPACE, "cs_beam_step: workspace not 8-byte aligned");
-  if (rows * plan.nsplit > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_beam_step: grid too large");
+  if (int rc = check_workspace(fn, workspace, workspace_bytes, need)) return rc;
+  if (int rc = check_grid(fn, rows * plan.nsplit)) return rc;
   char* wsb = static_cast<char*>(workspace);
-  auto* done_cnt = reinterpret_cast<uint32_t*>(wsb);
-  auto* row_cnt = reinterpret_cast<uint32_t*>(wsb + kBeamRowCntOff);
-  auto* wkey = reinterpret_cast<uint32_t*>(wsb + kBeamKeyOff);
+  const BeamCounters c = beam_counters(wsb);
   auto* part = reinterpret_cast<unsigned long long*>(wsb + kBeamCounterBytes);
   const int64_t ld_bytes = ld * elt_size(dtype);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool cap = softcap > 0.0f;
-  const bool fixed = fixed_lse_ok(softcap);
-  const float inv_cap = cap ? 1.0f / softcap : 0.0f;
-  int32_t n2 = 2;
-  while (n2 < C) n2 <<= 1;
+  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
+  const int32_t n2 = next_pow2(C);
   const char* lg = static_cast<const char*>(logits);
   // the same streaming arithmetic as cs_logsoftmax_gather (bit-identical lse): unsplit rows
   // one 1024-thread block x 2 vectors per lane, split rows the canonical split form
   // (split_partial), four splits per 1024-thread block
   const dim3 grid(static_cast<uint32_t>(rows * (plan.nsplit > 1 ? split_items(plan.nsplit, 1024) : 1)));
-#define CS_BEAM_LAUNCH(DTV, CAPV, FIXV)                                                           \
-  hipLaunchKernelGGL((beam_step_kernel<DTV, CAPV, FIXV, 1024, 2>), grid, dim3(1024), 0, st, lg,     \
-                     vocab, ld_bytes, plan.nsplit, plan.split_len, A, B, K, targets, rewards_in,  \
-                     softcap, inv_cap, welfare_kind, static_cast<double>(eps), part, row_cnt,     \
-                     done_cnt, wkey, out_U, out_W, n_order, n2, out_order, out_order_val, out_kept)
-  if (dtype == CS_F32) {
-    if (fixed) CS_BEAM_LAUNCH(CS_F32, true, true);
-    else if (cap) CS_BEAM_LAUNCH(CS_F32, true, false);
-    else CS_BEAM_LAUNCH(CS_F32, false, false);
-  } else if (dtype == CS_BF16) {
-    if (fixed) CS_BEAM_LAUNCH(CS_BF16, true, true);
-    else if (cap) CS_BEAM_LAUNCH(CS_BF16, true, false);
-    else CS_BEAM_LAUNCH(CS_BF16, false, false);
-  } else {
-    if (fixed) CS_BEAM_LAUNCH(CS_F16, true, true);
-    else if (cap) CS_BEAM_LAUNCH(CS_F16, true, false);
-    else CS_BEAM_LAUNCH(CS_F16, false, false);
-  }
-#undef CS_BEAM_LAUNCH
-  if (n_order > 0 && n2 > kFusedSort)
-    hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(256), static_cast<size_t>(n2) * sizeof(unsigned long long),
-                       st, out_W, static_cast<int32_t>(C), static_cast<int64_t>(C), n2, n_order,
-                       out_order, out_order_val);
+  dispatch_dtype_cap_fixed(dtype, softcap, [&](auto dt, auto cap, auto fixed) {
+    hipLaunchKernelGGL(
+        (beam_step_kernel<decltype(dt)::value, decltype(cap)::value, decltype(fixed)::value, 1024, 2>),
+        grid, dim3(1024), 0, st, lg, vocab, ld_bytes, plan.nsplit, plan.split_len, A, B, K, targets,
+        rewards_in, softcap, inv_cap, welfare_kind, static_cast<double>(eps), part, c.row_cnt,
+        c.done_cnt, c.wkey, out_U, out_W, n_order, n2, out_order, out_order_val, out_kept);
+  });
+  beam_sort_after(st, out_W, C, n2, n_order, out_order, out_order_val);
   return check_launch("cs_beam_step");
 }
 
@@ -1071,44 +1062,30 @@ int cs_beam_decode_step(const void* ref_logits, int64_t ld_ref, const void* logi
                         float* out_U, float* out_W, int32_t n_order, int32_t* out_order,
                         float* out_order_val, float* out_kept, void* workspace,
                         size_t workspace_bytes, cs_stream_t stream) {
-  const char* w = "cs_beam_decode_step: ";
-  if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)
-    return fail(CS_ERR_INVALID, std::string(w) + "unknown dtype");
-  if (A <= 0 || B <= 0 || K <= 0 || vocab <= 0 || ld < vocab || ld_ref < vocab)
-    return fail(CS_ERR_INVALID, std::string(w) + "need A, B, K > 0, vocab > 0, ld and ld_ref >= vocab");
-  if (K > 256 || K > vocab) return fail(CS_ERR_INVALID, std::string(w) + "need K <= min(256, vocab)");
+  const char* fn = "cs_beam_decode_step";
+  const std::string w = std::string(fn) + ": ";
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (ld_ref < vocab) return fail(CS_ERR_INVALID, w + "need ld_ref >= vocab");
+  if (A <= 0 || B <= 0 || K <= 0) return fail(CS_ERR_INVALID, w + "need A, B, K > 0");
+  if (K > 256 || K > vocab) return fail(CS_ERR_INVALID, w + "need K <= min(256, vocab)");
   const int64_t rows = static_cast<int64_t>(A) * B;
   const int64_t C = static_cast<int64_t>(B) * K;
-  if (C > 16384) return fail(CS_ERR_INVALID, std::string(w) + "B*K exceeds 16384");
-  if (rows > kBeamMaxRows || B > kBeamMaxBeams)
-    return fail(CS_ERR_INVALID, std::string(w) + "A*B exceeds 65536 or B exceeds 4096");
-  if (n_order < 0 || n_order > C) return fail(CS_ERR_INVALID, std::string(w) + "need 0 <= n_order <= B*K");
-  if (out_kept && (n_order == 0 || C > kFusedSort))
-    return fail(CS_ERR_INVALID, std::string(w) + "out_kept needs n_order > 0 and B*K <= 1024");
-  if (welfare_kind < CS_WELFARE_MIN || welfare_kind > CS_WELFARE_MAX)
-    return fail(CS_ERR_INVALID, std::string(w) + "unknown welfare kind");
-  if (!(softcap >= 0.0f) || std::isinf(softcap))
-    return fail(CS_ERR_INVALID, std::string(w) + "softcap must be finite and >= 0");
+  if (int rc = check_beam_args(fn, rows, C, n_order, out_kept, welfare_kind, softcap)) return rc;
+  if (B > kBeamMaxBeams) return fail(CS_ERR_INVALID, w + "B exceeds 4096");
   if (!ref_logits || !logits || !rewards_in || !out_ids || !out_U || !out_W ||
       (n_order > 0 && !out_order))
-    return fail(CS_ERR_INVALID, std::string(w) + "NULL pointer");
-  if (reinterpret_cast<uintptr_t>(logits) % elt_size(dtype) != 0 ||
-      reinterpret_cast<uintptr_t>(ref_logits) % elt_size(dtype) != 0)
-    return fail(CS_ERR_INVALID, std::string(w) + "logits not element-aligned");
+    return fail(CS_ERR_INVALID, w + "NULL pointer");
+  if (int rc = check_elt_aligned(fn, logits, dtype)) return rc;
+  if (int rc = check_elt_aligned(fn, ref_logits, dtype)) return rc;
   const DecodeLayout d = decode_layout(A, B, vocab, K, dtype);
   if (static_cast<int64_t>(d.nchunk_p) * K > 16384)
-    return fail(CS_ERR_INVALID, std::string(w) + "proposer chunks x K exceeds 16384");
-  if (!workspace || workspace_bytes < d.total)
-    return fail(CS_ERR_WORKSPACE, std::string(w) + "workspace smaller than cs_beam_decode_workspace_size()");
-  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return fail(CS_ERR_WORKSPACE, std::string(w) + "workspace not 8-byte aligned");
+    return fail(CS_ERR_INVALID, w + "proposer chunks x K exceeds 16384");
+  if (int rc = check_workspace(fn, workspace, workspace_bytes, d.total)) return rc;
   const int64_t row_blocks = rows * (d.plan.nsplit > 1 ? split_items(d.plan.nsplit, kDecodeBlock) : 1);
   const int64_t grid = static_cast<int64_t>(B) * d.nchunk_p + row_blocks;
-  if (grid > 0x7fffffffLL) return fail(CS_ERR_INVALID, std::string(w) + "grid too large");
+  if (int rc = check_grid(fn, grid)) return rc;
   char* wsb = static_cast<char*>(workspace);
-  auto* done_cnt = reinterpret_cast<uint32_t*>(wsb);
-  auto* row_cnt = reinterpret_cast<uint32_t*>(wsb + kBeamRowCntOff);
-  auto* wkey = reinterpret_cast<uint32_t*>(wsb + kBeamKeyOff);
+  const BeamCounters c = beam_counters(wsb);
   auto* prop_cnt = reinterpret_cast<uint32_t*>(wsb + kBeamCounterBytes);
   auto* beam_cnt = prop_cnt + kBeamMaxBeams;
   auto* lse_ws = reinterpret_cast<uint32_t*>(wsb + d.lse_off);
@@ -1117,49 +1094,29 @@ int cs_beam_decode_step(const void* ref_logits, int64_t ld_ref, const void* logi
   auto* part = reinterpret_cast<unsigned long long*>(wsb + d.part_off);
   const int64_t esz = elt_size(dtype);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool cap = softcap > 0.0f;
-  const bool fixed = fixed_lse_ok(softcap);
-  const float inv_cap = cap ? 1.0f / softcap : 0.0f;
-  int32_t n2 = 2;
-  while (n2 < C) n2 <<= 1;
+  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
+  const int32_t n2 = next_pow2(C);
   const char* rg = static_cast<const char*>(ref_logits);
   const char* lg = static_cast<const char*>(logits);
   const int32_t rows_first = decode_rows_first(row_blocks);
   // 16-byte vector loads in the proposer when every reference row starts 16-B aligned
   const int32_t ref_vec = (reinterpret_cast<uintptr_t>(ref_logits) % 16 == 0 &&
                            (ld_ref * esz) % 16 == 0) ? 1 : 0;
-#define CS_DECODE_GO(DTV, CAPV, FIXV, KPV)                                                         \
-  hipLaunchKernelGGL((beam_decode_kernel<DTV, CAPV, FIXV, kDecodeBlock, kDecodeUnroll, KPV>),      \
-                     dim3(grid), dim3(kDecodeBlock), 0,                                            \
-                     st, rg, ld_ref * esz, d.nchunk_p, rows_first, ref_vec, lg, vocab, ld * esz,   \
-                     d.plan.nsplit, d.plan.split_len, A, B, K, rewards_in, softcap, inv_cap,       \
-                     welfare_kind, static_cast<double>(eps), part, ppart, row_cnt, prop_cnt,       \
-                     beam_cnt, done_cnt, wkey, lse_ws, ids_ws, out_ids, out_U, out_W, n_order, n2, \
-                     out_order, out_order_val, out_kept)
-#define CS_DECODE_LAUNCH(DTV, CAPV, FIXV)                        \
-  do {                                                           \
-    if (d.kp == 4) CS_DECODE_GO(DTV, CAPV, FIXV, 4);             \
-    else CS_DECODE_GO(DTV, CAPV, FIXV, kp1024(DTV));             \
-  } while (0)
-  if (dtype == CS_F32) {
-    if (fixed) CS_DECODE_LAUNCH(CS_F32, true, true);
-    else if (cap) CS_DECODE_LAUNCH(CS_F32, true, false);
-    else CS_DECODE_LAUNCH(CS_F32, false, false);
-  } else if (dtype == CS_BF16) {
-    if (fixed) CS_DECODE_LAUNCH(CS_BF16, true, true);
-    else if (cap) CS_DECODE_LAUNCH(CS_BF16, true, false);
-    else CS_DECODE_LAUNCH(CS_BF16, false, false);
-  } else {
-    if (fixed) CS_DECODE_LAUNCH(CS_F16, true, true);
-    else if (cap) CS_DECODE_LAUNCH(CS_F16, true, false);
-    else CS_DECODE_LAUNCH(CS_F16, false, false);
-  }
-#undef CS_DECODE_LAUNCH
-#undef CS_DECODE_GO
-  if (n_order > 0 && n2 > kFusedSort)
-    hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(256), static_cast<size_t>(n2) * sizeof(unsigned long long),
-                       st, out_W, static_cast<int32_t>(C), static_cast<int64_t>(C), n2, n_order,
-                       out_order, out_order_val);
+  dispatch_dtype_cap_fixed(dtype, softcap, [&](auto dt, auto cap, auto fixed) {
+    constexpr int DT = decltype(dt)::value;
+    auto go = [&](auto kp) {
+      hipLaunchKernelGGL((beam_decode_kernel<DT, decltype(cap)::value, decltype(fixed)::value, kDecodeBlock,
+                                             kDecodeUnroll, decltype(kp)::value>),
+                         dim3(grid), dim3(kDecodeBlock), 0, st, rg, ld_ref * esz, d.nchunk_p, rows_first,
+                         ref_vec, lg, vocab, ld * esz, d.plan.nsplit, d.plan.split_len, A, B, K,
+                         rewards_in, softcap, inv_cap, welfare_kind, static_cast<double>(eps), part,
+                         ppart, c.row_cnt, prop_cnt, beam_cnt, c.done_cnt, c.wkey, lse_ws, ids_ws,
+                         out_ids, out_U, out_W, n_order, n2, out_order, out_order_val, out_kept);
+    };
+    if (d.kp == 4) go(std::integral_constant<int, 4>{});
+    else go(std::integral_constant<int, kp1024(DT)>{});
+  });
+  beam_sort_after(st, out_W, C, n2, n_order, out_order, out_order_val);
   return check_launch("cs_beam_decode_step");
 }
 

@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "consensus_scoring.h"
 
@@ -53,6 +54,45 @@ inline int check_launch(const char* what) {
     return fail(CS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   }
   return CS_OK;
+}
+
+// Argument checks shared by the entry points that stream whole logits rows
+// (cs_logsoftmax_gather, cs_vocab_topk, cs_vocab_sample, cs_beam_step, cs_beam_decode_step).
+// `fn` is the entry point's name; each returns CS_OK or the status after fail().
+inline int check_logits(const char* fn, int dtype, int64_t vocab, int64_t ld) {
+  if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": unknown dtype");
+  if (vocab <= 0 || ld < vocab)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need vocab > 0 and ld >= vocab");
+  return CS_OK;
+}
+inline int check_elt_aligned(const char* fn, const void* logits, int dtype) {
+  if (reinterpret_cast<uintptr_t>(logits) % (dtype == CS_F32 ? 4 : 2) != 0)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": logits not element-aligned");
+  return CS_OK;
+}
+inline int check_softcap(const char* fn, float softcap) {
+  if (!(softcap >= 0.0f) || std::isinf(softcap))
+    return fail(CS_ERR_INVALID, std::string(fn) + ": softcap must be finite and >= 0");
+  return CS_OK;
+}
+// `align`: 8 wherever the workspace holds 64-bit hand-off words
+inline int check_workspace(const char* fn, const void* ws, size_t have, size_t need, int align = 8) {
+  if (!ws || have < need)
+    return fail(CS_ERR_WORKSPACE, std::string(fn) + ": workspace smaller than its workspace_size()");
+  if (reinterpret_cast<uintptr_t>(ws) % align != 0)
+    return fail(CS_ERR_WORKSPACE, std::string(fn) + ": workspace not 8-byte aligned");
+  return CS_OK;
+}
+inline int check_grid(const char* fn, int64_t blocks) {
+  if (blocks > 0x7fffffffLL) return fail(CS_ERR_INVALID, std::string(fn) + ": grid too large");
+  return CS_OK;
+}
+// the smallest power of two >= max(n, 2): the length a bitonic sort of n keys runs over
+inline int32_t next_pow2(int64_t n) {
+  int32_t n2 = 2;
+  while (n2 < n) n2 <<= 1;
+  return n2;
 }
 
 // ---------------------------------------------------------------------------
@@ -443,6 +483,33 @@ __device__ __forceinline__ int32_t split_count(int32_t item, int32_t nsplit, int
 // The fixed-offset sum is exact enough and cannot overflow for |x'| <= 60:
 // e^60 * 2^31 < FLT_MAX and e^-60 is a normal float.
 inline bool fixed_lse_ok(float cap) { return cap > 0.0f && cap <= 60.0f; }
+
+// Host dispatch of the streaming kernels' template arguments: the run-time (dtype, softcap)
+// as compile-time constants, f(dt, cap) with DT = decltype(dt)::value, CAP = decltype(cap)::value.
+template <typename F>
+inline void dispatch_dtype_cap(int dtype, float softcap, F&& f) {
+  auto go = [&](auto dt) {
+    if (softcap > 0.0f) f(dt, std::true_type{});
+    else f(dt, std::false_type{});
+  };
+  if (dtype == CS_F32) go(std::integral_constant<int, CS_F32>{});
+  else if (dtype == CS_BF16) go(std::integral_constant<int, CS_BF16>{});
+  else go(std::integral_constant<int, CS_F16>{});
+}
+// ... and FIXED = fixed_lse_ok(softcap) as f's third argument; looked at only under CAP, so
+// <DT, false, true> is never instantiated
+template <typename F>
+inline void dispatch_dtype_cap_fixed(int dtype, float softcap, F&& f) {
+  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
+    if constexpr (decltype(cap)::value) {
+      if (fixed_lse_ok(softcap)) {
+        f(dt, cap, std::true_type{});
+        return;
+      }
+    }
+    f(dt, cap, std::false_type{});
+  });
+}
 
 // Order key: larger float -> larger key; NaN below everything; -0 == +0.
 __device__ __forceinline__ uint32_t order_key(float f) {

@@ -290,37 +290,33 @@ size_t cs_vocab_topk_workspace_size(int64_t rows, int64_t vocab, int32_t k) {
 int cs_vocab_topk(const void* logits, int dtype, int64_t rows, int64_t vocab, int64_t ld, int32_t k,
                   float softcap, int32_t* out_ids, float* out_vals, void* workspace,
                   size_t workspace_bytes, cs_stream_t stream) {
-  if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)
-    return fail(CS_ERR_INVALID, "cs_vocab_topk: unknown dtype");
-  if (rows < 0 || vocab <= 0 || ld < vocab || k <= 0 || k > 256 || k > vocab)
-    return fail(CS_ERR_INVALID, "cs_vocab_topk: need rows >= 0, vocab > 0, ld >= vocab, 0 < k <= min(256, vocab)");
-  if (!(softcap >= 0.0f) || std::isinf(softcap))
-    return fail(CS_ERR_INVALID, "cs_vocab_topk: softcap must be finite and >= 0");
+  const char* fn = "cs_vocab_topk";
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (rows < 0 || k <= 0 || k > 256 || k > vocab)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need rows >= 0 and 0 < k <= min(256, vocab)");
+  if (int rc = check_softcap(fn, softcap)) return rc;
   if (rows == 0) return CS_OK;
-  if (!logits || !out_ids) return fail(CS_ERR_INVALID, "cs_vocab_topk: NULL pointer");
+  if (!logits || !out_ids) return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
   const int32_t nchunk = topk_nchunk(vocab);
   const int64_t nkeys = static_cast<int64_t>(nchunk) * (k < kTopkChunk ? k : kTopkChunk);
-  if (nkeys > 16384) return fail(CS_ERR_INVALID, "cs_vocab_topk: vocab chunks x k exceeds 16384");
-  if (rows * nchunk > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_vocab_topk: grid too large");
-  const size_t need = cs_vocab_topk_workspace_size(rows, vocab, k);
-  if (!workspace || workspace_bytes < need)
-    return fail(CS_ERR_WORKSPACE, "cs_vocab_topk: workspace smaller than cs_vocab_topk_workspace_size()");
+  if (nkeys > 16384) return fail(CS_ERR_INVALID, std::string(fn) + ": vocab chunks x k exceeds 16384");
+  if (int rc = check_grid(fn, rows * nchunk)) return rc;
+  // (the chunk winners are 64-bit words, but this entry point has never asked for an aligned
+  // workspace)
+  if (int rc = check_workspace(fn, workspace, workspace_bytes,
+                               cs_vocab_topk_workspace_size(rows, vocab, k), 1))
+    return rc;
   auto* part = static_cast<unsigned long long*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t ld_bytes = ld * elt_size(dtype);
   const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
-  const dim3 g1(static_cast<uint32_t>(rows * nchunk));
   const char* lg = static_cast<const char*>(logits);
-#define CS_TOPK_LAUNCH(DTV, CAPV)                                                               \
-  hipLaunchKernelGGL((vocab_topk_chunk_kernel<DTV, CAPV>), g1, dim3(256), 0, st, lg, vocab,    \
-                     ld_bytes, nchunk, k, softcap, inv_cap, part)
-  const bool cap = softcap > 0.0f;
-  if (dtype == CS_F32) { if (cap) CS_TOPK_LAUNCH(CS_F32, true); else CS_TOPK_LAUNCH(CS_F32, false); }
-  else if (dtype == CS_BF16) { if (cap) CS_TOPK_LAUNCH(CS_BF16, true); else CS_TOPK_LAUNCH(CS_BF16, false); }
-  else { if (cap) CS_TOPK_LAUNCH(CS_F16, true); else CS_TOPK_LAUNCH(CS_F16, false); }
-#undef CS_TOPK_LAUNCH
-  int32_t n2 = 2;
-  while (n2 < nkeys) n2 <<= 1;
+  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
+    hipLaunchKernelGGL((vocab_topk_chunk_kernel<decltype(dt)::value, decltype(cap)::value>),
+                       dim3(static_cast<uint32_t>(rows * nchunk)), dim3(256), 0, st, lg, vocab,
+                       ld_bytes, nchunk, k, softcap, inv_cap, part);
+  });
+  const int32_t n2 = next_pow2(nkeys);
   const int32_t lds_keys = n2 > kTopkChunk ? n2 : kTopkChunk;
   hipLaunchKernelGGL(vocab_topk_merge_kernel, dim3(static_cast<uint32_t>(rows)), dim3(256),
                      static_cast<size_t>(lds_keys) * sizeof(unsigned long long), st, part,
@@ -338,23 +334,20 @@ int cs_vocab_sample(const void* logits, int dtype, int64_t rows, int64_t vocab, 
                     float temperature, float softcap, const uint64_t* seeds, int32_t n_draw,
                     int32_t* out_ids, float* out_lp, void* workspace, size_t workspace_bytes,
                     cs_stream_t stream) {
-  if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)
-    return fail(CS_ERR_INVALID, "cs_vocab_sample: unknown dtype");
-  if (rows < 0 || vocab <= 0 || ld < vocab || n_draw <= 0 || n_draw > kMaxDraws)
-    return fail(CS_ERR_INVALID, "cs_vocab_sample: need rows >= 0, vocab > 0, ld >= vocab, 0 < n_draw <= 16");
+  const char* fn = "cs_vocab_sample";
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (rows < 0 || n_draw <= 0 || n_draw > kMaxDraws)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need rows >= 0 and 0 < n_draw <= 16");
   if (!(temperature > 0.0f) || std::isinf(temperature))
-    return fail(CS_ERR_INVALID, "cs_vocab_sample: temperature must be finite and > 0");
-  if (!(softcap >= 0.0f) || std::isinf(softcap))
-    return fail(CS_ERR_INVALID, "cs_vocab_sample: softcap must be finite and >= 0");
+    return fail(CS_ERR_INVALID, std::string(fn) + ": temperature must be finite and > 0");
+  if (int rc = check_softcap(fn, softcap)) return rc;
   if (rows == 0) return CS_OK;
-  if (!logits || !seeds || !out_ids) return fail(CS_ERR_INVALID, "cs_vocab_sample: NULL pointer");
+  if (!logits || !seeds || !out_ids) return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
   const SplitPlan plan = plan_split(rows, vocab, CS_F32);
-  if (rows * plan.nsplit > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_vocab_sample: grid too large");
-  const size_t need = cs_vocab_sample_workspace_size(rows, vocab, n_draw);
-  if (!workspace || workspace_bytes < need)
-    return fail(CS_ERR_WORKSPACE, "cs_vocab_sample: workspace smaller than cs_vocab_sample_workspace_size()");
-  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return fail(CS_ERR_WORKSPACE, "cs_vocab_sample: workspace not 8-byte aligned");
+  if (int rc = check_grid(fn, rows * plan.nsplit)) return rc;
+  if (int rc = check_workspace(fn, workspace, workspace_bytes,
+                               cs_vocab_sample_workspace_size(rows, vocab, n_draw)))
+    return rc;
   auto* lse_part = static_cast<float2*>(workspace);
   auto* draw_part = reinterpret_cast<DrawBest*>(lse_part + rows * plan.nsplit);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -363,21 +356,16 @@ int cs_vocab_sample(const void* logits, int dtype, int64_t rows, int64_t vocab, 
   const float inv_t = 1.0f / temperature;
   const char* lg = static_cast<const char*>(logits);
   const auto* sd = reinterpret_cast<const unsigned long long*>(seeds);
-  const dim3 g1(static_cast<uint32_t>(rows * plan.nsplit)), g2(static_cast<uint32_t>(rows));
-#define CS_SAMPLE_LAUNCH(DTV, CAPV)                                                              \
-  do {                                                                                          \
-    hipLaunchKernelGGL((vocab_sample_kernel<DTV, CAPV>), g1, dim3(256), 0, st, lg, vocab,       \
-                       ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap, sd,      \
-                       n_draw, lse_part, draw_part);                                            \
-    hipLaunchKernelGGL((vocab_sample_merge_kernel<DTV, CAPV>), g2, dim3(64), 0, st, lg,         \
-                       ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part, draw_part,     \
-                       n_draw, out_ids, out_lp);                                                \
-  } while (0)
-  const bool cap = softcap > 0.0f;
-  if (dtype == CS_F32) { if (cap) CS_SAMPLE_LAUNCH(CS_F32, true); else CS_SAMPLE_LAUNCH(CS_F32, false); }
-  else if (dtype == CS_BF16) { if (cap) CS_SAMPLE_LAUNCH(CS_BF16, true); else CS_SAMPLE_LAUNCH(CS_BF16, false); }
-  else { if (cap) CS_SAMPLE_LAUNCH(CS_F16, true); else CS_SAMPLE_LAUNCH(CS_F16, false); }
-#undef CS_SAMPLE_LAUNCH
+  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
+    constexpr int DT = decltype(dt)::value;
+    constexpr bool CAP = decltype(cap)::value;
+    hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows * plan.nsplit)),
+                       dim3(256), 0, st, lg, vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t,
+                       softcap, inv_cap, sd, n_draw, lse_part, draw_part);
+    hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows)), dim3(64),
+                       0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part, draw_part,
+                       n_draw, out_ids, out_lp);
+  });
   return check_launch("cs_vocab_sample");
 }
 

@@ -100,58 +100,26 @@ __global__ __launch_bounds__(kMergeBlock) void lsg_merge_kernel(
 //   single pass (rows >= 2048): 1024 threads x 2 vectors in flight  (C2: 7.25 TB/s, 90.6 %)
 //   split-V (fewer rows):        the canonical split arithmetic (split_partial, cs_kernels.cuh):
 //                                256-thread sub-blocks x 2 vectors, 4 splits per 1024 threads
-template <int DT, bool CAP, int BLOCK, int UNROLL>
-void launch_stream(const void* logits, int64_t items, int64_t vocab, int64_t ld_bytes,
-                   const SplitPlan& plan, const int32_t* tgt, int32_t k, float cap, float inv_cap,
-                   float* out_tok, float* out_lse, float2* part, hipStream_t st) {
-  const char* lg = static_cast<const char*>(logits);
-  if constexpr (CAP) {
-    if (fixed_lse_ok(cap)) {
-      hipLaunchKernelGGL((lsg_stream_kernel<DT, CAP, true, BLOCK, UNROLL>),
-                         dim3(static_cast<uint32_t>(items)), dim3(BLOCK), 0, st, lg, items, vocab,
-                         ld_bytes, plan.nsplit, plan.split_len, tgt, k, cap, inv_cap, out_tok,
-                         out_lse, part);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((lsg_stream_kernel<DT, CAP, false, BLOCK, UNROLL>),
-                       dim3(static_cast<uint32_t>(items)), dim3(BLOCK), 0, st, lg, items, vocab,
-                       ld_bytes, plan.nsplit, plan.split_len, tgt, k, cap, inv_cap, out_tok,
-                       out_lse, part);
-}
-
-template <int DT, bool CAP>
+template <int DT, bool CAP, bool FIXED>
 void launch_lsg(const void* logits, int64_t rows, int64_t vocab, int64_t ld_bytes,
                 const SplitPlan& plan, const int32_t* tgt, int32_t k, float cap, float* out_tok,
-                float* out_lse, float2* part, hipStream_t st, bool finish = true) {
+                float* out_lse, float2* part, hipStream_t st) {
   const float inv_cap = CAP ? 1.0f / cap : 0.0f;
-  const int64_t items = rows * plan.nsplit;
+  const char* lg = static_cast<const char*>(logits);
   if (plan.nsplit == 1) {
-    launch_stream<DT, CAP, 1024, 2>(logits, items, vocab, ld_bytes, plan, tgt, k, cap, inv_cap,
-                                    out_tok, out_lse, part, st);
-  } else {
-    // the canonical split arithmetic, four splits per 1024-thread workgroup
-    const int64_t n_items = rows * split_items(plan.nsplit, 1024);
-    const char* lg = static_cast<const char*>(logits);
-    bool done = false;
-    if constexpr (CAP) {
-      if (fixed_lse_ok(cap)) {
-        hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, true, 1024>),
-                           dim3(static_cast<uint32_t>(n_items)), dim3(1024), 0, st, lg, n_items,
-                           vocab, ld_bytes, plan.nsplit, plan.split_len, cap, inv_cap, part);
-        done = true;
-      }
-    }
-    if (!done)
-      hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, false, 1024>),
-                         dim3(static_cast<uint32_t>(n_items)), dim3(1024), 0, st, lg, n_items,
-                         vocab, ld_bytes, plan.nsplit, plan.split_len, cap, inv_cap, part);
+    hipLaunchKernelGGL((lsg_stream_kernel<DT, CAP, FIXED, 1024, 2>), dim3(static_cast<uint32_t>(rows)),
+                       dim3(1024), 0, st, lg, rows, vocab, ld_bytes, plan.nsplit, plan.split_len, tgt,
+                       k, cap, inv_cap, out_tok, out_lse, part);
+    return;
   }
-  if (plan.nsplit > 1 && finish) {
-    hipLaunchKernelGGL((lsg_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows)),
-                       dim3(kMergeBlock), 0, st, static_cast<const char*>(logits), vocab, ld_bytes,
-                       plan.nsplit, part, tgt, k, cap, inv_cap, out_tok, out_lse);
-  }
+  // the canonical split arithmetic, four splits per 1024-thread workgroup
+  const int64_t n_items = rows * split_items(plan.nsplit, 1024);
+  hipLaunchKernelGGL((lsg_split_kernel<DT, CAP, FIXED, 1024>), dim3(static_cast<uint32_t>(n_items)),
+                     dim3(1024), 0, st, lg, n_items, vocab, ld_bytes, plan.nsplit, plan.split_len, cap,
+                     inv_cap, part);
+  hipLaunchKernelGGL((lsg_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows)), dim3(kMergeBlock),
+                     0, st, lg, vocab, ld_bytes, plan.nsplit, part, tgt, k, cap, inv_cap, out_tok,
+                     out_lse);
 }
 
 }  // namespace
@@ -175,60 +143,30 @@ int cs_logsoftmax_gather(const void* logits, int dtype, int64_t rows, int64_t vo
                          const int32_t* target_ids, int32_t k, float softcap, float* out_tok_lp,
                          float* out_row_lse, void* workspace, size_t workspace_bytes,
                          cs_stream_t stream) {
-  if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)
-    return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: unknown dtype");
-  if (rows < 0 || vocab <= 0 || ld < vocab || k < 0)
-    return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: need rows >= 0, vocab > 0, ld >= vocab, k >= 0");
-  if (rows > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: rows exceeds 2^31-1");
+  const char* fn = "cs_logsoftmax_gather";
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (rows < 0 || k < 0) return fail(CS_ERR_INVALID, std::string(fn) + ": need rows >= 0 and k >= 0");
+  if (rows > 0x7fffffffLL) return fail(CS_ERR_INVALID, std::string(fn) + ": rows exceeds 2^31-1");
   if (rows == 0) return CS_OK;
-  if (!logits) return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: logits is NULL");
+  if (!logits) return fail(CS_ERR_INVALID, std::string(fn) + ": logits is NULL");
   if (k > 0 && (!target_ids || !out_tok_lp))
-    return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: k > 0 needs target_ids and out_tok_lp");
-  if (!(softcap >= 0.0f) || std::isinf(softcap))
-    return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: softcap must be finite and >= 0");
-  if (reinterpret_cast<uintptr_t>(logits) % elt_size(dtype) != 0)
-    return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: logits not element-aligned");
+    return fail(CS_ERR_INVALID, std::string(fn) + ": k > 0 needs target_ids and out_tok_lp");
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  if (int rc = check_elt_aligned(fn, logits, dtype)) return rc;
   const SplitPlan plan = plan_split(rows, vocab, dtype);
-  const int64_t grid = rows * plan.nsplit;
-  if (grid > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_logsoftmax_gather: grid too large");
+  if (int rc = check_grid(fn, rows * plan.nsplit)) return rc;
   float2* part = nullptr;
   if (plan.nsplit > 1) {
     const size_t need = static_cast<size_t>(rows) * plan.nsplit * sizeof(float2);
-    if (!workspace || workspace_bytes < need)
-      return fail(CS_ERR_WORKSPACE, "cs_logsoftmax_gather: workspace smaller than cs_workspace_size()");
-    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-      return fail(CS_ERR_WORKSPACE, "cs_logsoftmax_gather: workspace not 8-byte aligned");
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, need)) return rc;
     part = static_cast<float2*>(workspace);
   }
   const int64_t ld_bytes = ld * elt_size(dtype);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool cap = softcap > 0.0f;
-  switch (dtype) {
-    case CS_F32:
-      if (cap)
-        launch_lsg<CS_F32, true>(logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap,
-                                 out_tok_lp, out_row_lse, part, st);
-      else
-        launch_lsg<CS_F32, false>(logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap,
-                                  out_tok_lp, out_row_lse, part, st);
-      break;
-    case CS_BF16:
-      if (cap)
-        launch_lsg<CS_BF16, true>(logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap,
-                                  out_tok_lp, out_row_lse, part, st);
-      else
-        launch_lsg<CS_BF16, false>(logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap,
-                                   out_tok_lp, out_row_lse, part, st);
-      break;
-    default:
-      if (cap)
-        launch_lsg<CS_F16, true>(logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap,
-                                 out_tok_lp, out_row_lse, part, st);
-      else
-        launch_lsg<CS_F16, false>(logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap,
-                                  out_tok_lp, out_row_lse, part, st);
-      break;
-  }
+  dispatch_dtype_cap_fixed(dtype, softcap, [&](auto dt, auto cap, auto fixed) {
+    launch_lsg<decltype(dt)::value, decltype(cap)::value, decltype(fixed)::value>(
+        logits, rows, vocab, ld_bytes, plan, target_ids, k, softcap, out_tok_lp, out_row_lse, part,
+        static_cast<hipStream_t>(stream));
+  });
   return check_launch("cs_logsoftmax_gather");
 }
 

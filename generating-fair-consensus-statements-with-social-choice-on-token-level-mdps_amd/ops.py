@@ -83,6 +83,34 @@ _beam_ws: dict = {}
 _decode_ws: dict = {}
 
 
+def _workspace_args(workspace: Optional[Workspace], pool: dict, nbytes: int, device: torch.device,
+                    counters_of: Optional[str] = None):
+    """The workspace arguments of an entry point: (workspace, pointer or None, byte size), from
+    the caller's Workspace or the device's default in ``pool``.  ``counters_of`` names an op that
+    keeps arrival counters there and so needs a zeroed Workspace."""
+    if workspace is None:
+        workspace = pool.setdefault(device, Workspace(zeroed=counters_of is not None))
+    if counters_of is not None and not workspace.zeroed:
+        raise CSError(f"{counters_of} needs a Workspace(zeroed=True) of its own (arrival counters)")
+    buf = workspace.get(nbytes, device)
+    if buf is None:
+        return workspace, None, 0
+    return workspace, buf.data_ptr(), buf.numel()
+
+
+def _logits_args(logits: torch.Tensor, vocab: Optional[int]):
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise CSError("logits must be 2-D with unit column stride")
+    if logits.dtype not in _DTYPE:
+        raise CSError(f"unsupported logits dtype {logits.dtype}")
+    rows = logits.shape[0]
+    ld = logits.stride(0) if rows > 1 else logits.shape[1]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    if vocab > logits.shape[1]:
+        raise CSError("vocab exceeds logits width")
+    return rows, ld, vocab
+
+
 def workspace_size(rows: int, vocab: int, k: int = 1) -> int:
     return int(_lib.load().cs_workspace_size(rows, vocab, k))
 
@@ -102,14 +130,7 @@ def logsoftmax_gather(logits: torch.Tensor, targets: Optional[torch.Tensor], *, 
     (src/utils.py:249-263); core.log_softmax_rows + gather (core.py:64-68, 89-90).
     """
     L = _lib.load()
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise CSError("logits must be 2-D with unit column stride")
-    if logits.dtype not in _DTYPE:
-        raise CSError(f"unsupported logits dtype {logits.dtype}")
-    rows, ld = logits.shape[0], logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
-    vocab = logits.shape[1] if vocab is None else int(vocab)
-    if vocab > logits.shape[1]:
-        raise CSError("vocab exceeds logits width")
+    rows, ld, vocab = _logits_args(logits, vocab)
     if targets is None:
         k = 0
         targets = torch.empty((rows, 0), dtype=torch.int32, device=logits.device)
@@ -130,15 +151,12 @@ def logsoftmax_gather(logits: torch.Tensor, targets: Optional[torch.Tensor], *, 
         raise CSError("out must be contiguous float32 with rows*k elements")
     if lse_out is None and want_lse:
         lse_out = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    nbytes = workspace_size(rows, vocab, k)
-    if workspace is None:
-        workspace = _default_ws.setdefault(logits.device, Workspace())
-    ws = workspace.get(nbytes, logits.device)
+    _, ws_ptr, ws_bytes = _workspace_args(workspace, _default_ws, workspace_size(rows, vocab, k),
+                                          logits.device)
     rc = L.cs_logsoftmax_gather(
         logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld,
         targets.data_ptr() if k else None, k, float(softcap), out.data_ptr() if k else None,
-        lse_out.data_ptr() if lse_out is not None else None,
-        ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream())
+        lse_out.data_ptr() if lse_out is not None else None, ws_ptr, ws_bytes, _stream())
     _lib.check(rc, "cs_logsoftmax_gather")
     return out, lse_out
 
@@ -255,6 +273,27 @@ def beam_select(W: torch.Tensor, n_order: int, *, U: Optional[torch.Tensor] = No
     return order, val
 
 
+def _beam_outputs(A: int, C: int, n_order: int, dev: torch.device, out_U, out_W, kept_out,
+                  out_order=None):
+    """(U, W, order, order_val) of a beam step: the caller's tensors, validated, or new ones."""
+    U = torch.empty((A, C), dtype=torch.float32, device=dev) if out_U is None else out_U
+    W = torch.empty(C, dtype=torch.float32, device=dev) if out_W is None else out_W
+    if (U.shape != (A, C) or W.shape != (C,) or U.dtype != torch.float32 or
+            W.dtype != torch.float32 or not U.is_contiguous() or not W.is_contiguous()):
+        raise CSError(f"out_U / out_W must be contiguous float32 [{A}, {C}] / [{C}]")
+    order = (torch.empty(max(n_order, 0), dtype=torch.int32, device=dev) if out_order is None
+             else out_order)
+    if order.shape != (max(n_order, 0),) or order.dtype != torch.int32 or not order.is_contiguous():
+        raise CSError(f"out_order must be a contiguous int32 [{n_order}] tensor")
+    oval = torch.empty(max(n_order, 0), dtype=torch.float32, device=dev)
+    if kept_out is not None:
+        if (kept_out.dtype != torch.float32 or not kept_out.is_contiguous()
+                or tuple(kept_out.shape) != (A, n_order)):
+            raise CSError(f"kept_out must be a contiguous float32 [{A}, {n_order}] tensor")
+        _require_cuda(kept_out)
+    return U, W, order, oval
+
+
 def beam_step(logits: torch.Tensor, targets: torch.Tensor, rewards: torch.Tensor, kind="min", *,
               n_order: Optional[int] = None, vocab: Optional[int] = None, softcap: float = 0.0,
               eps: float = 1e-9, workspace: Optional[Workspace] = None,
@@ -293,31 +332,15 @@ def beam_step(logits: torch.Tensor, targets: torch.Tensor, rewards: torch.Tensor
     C = B * K
     n_order = C if n_order is None else int(n_order)
     dev = logits.device
-    U = torch.empty((A, C), dtype=torch.float32, device=dev) if out_U is None else out_U
-    W = torch.empty(C, dtype=torch.float32, device=dev) if out_W is None else out_W
-    if (U.shape != (A, C) or W.shape != (C,) or U.dtype != torch.float32 or
-            W.dtype != torch.float32 or not U.is_contiguous() or not W.is_contiguous()):
-        raise CSError(f"out_U / out_W must be contiguous float32 [{A}, {C}] / [{C}]")
-    order = torch.empty(max(n_order, 0), dtype=torch.int32, device=dev)
-    oval = torch.empty(max(n_order, 0), dtype=torch.float32, device=dev)
-    nbytes = int(L.cs_beam_step_workspace_size(rows, vocab))
-    if workspace is None:
-        workspace = _beam_ws.setdefault(dev, Workspace(zeroed=True))
-    if not workspace.zeroed:
-        raise CSError("beam_step needs a Workspace(zeroed=True) of its own (arrival counters)")
-    ws = workspace.get(nbytes, dev)
-    if kept_out is not None:
-        if (kept_out.dtype != torch.float32 or not kept_out.is_contiguous()
-                or tuple(kept_out.shape) != (A, n_order)):
-            raise CSError(f"kept_out must be a contiguous float32 [{A}, {n_order}] tensor")
-        _require_cuda(kept_out)
+    U, W, order, oval = _beam_outputs(A, C, n_order, dev, out_U, out_W, kept_out)
+    workspace, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _beam_ws, int(L.cs_beam_step_workspace_size(rows, vocab)), dev, "beam_step")
     rc = L.cs_beam_step(logits.data_ptr(), _DTYPE[logits.dtype], A, B, vocab, ld,
                         targets.data_ptr(), K, rewards.data_ptr(), float(softcap), int(kind),
                         float(eps), U.data_ptr(), W.data_ptr(), n_order,
                         order.data_ptr() if n_order else None, oval.data_ptr() if n_order else None,
                         kept_out.data_ptr() if kept_out is not None else None,
-                        ws.data_ptr() if ws is not None else None,
-                        ws.numel() if ws is not None else 0, _stream())
+                        ws_ptr, ws_bytes, _stream())
     if rc != 0:
         workspace.reset()
     _lib.check(rc, "cs_beam_step")
@@ -362,27 +385,10 @@ def beam_decode_step(ref_logits: torch.Tensor, logits: torch.Tensor, rewards: to
     ids = torch.empty((B, k), dtype=torch.int32, device=dev) if out_ids is None else out_ids
     if ids.shape != (B, k) or ids.dtype != torch.int32 or not ids.is_contiguous():
         raise CSError(f"out_ids must be a contiguous int32 [{B}, {k}] tensor")
-    U = torch.empty((A, C), dtype=torch.float32, device=dev) if out_U is None else out_U
-    W = torch.empty(C, dtype=torch.float32, device=dev) if out_W is None else out_W
-    if (U.shape != (A, C) or W.shape != (C,) or U.dtype != torch.float32 or
-            W.dtype != torch.float32 or not U.is_contiguous() or not W.is_contiguous()):
-        raise CSError(f"out_U / out_W must be contiguous float32 [{A}, {C}] / [{C}]")
-    order = (torch.empty(max(n_order, 0), dtype=torch.int32, device=dev) if out_order is None
-             else out_order)
-    if order.shape != (max(n_order, 0),) or order.dtype != torch.int32 or not order.is_contiguous():
-        raise CSError(f"out_order must be a contiguous int32 [{n_order}] tensor")
-    oval = torch.empty(max(n_order, 0), dtype=torch.float32, device=dev)
-    nbytes = int(L.cs_beam_decode_workspace_size(A, B, vocab, k))
-    if workspace is None:
-        workspace = _decode_ws.setdefault(dev, Workspace(zeroed=True))
-    if not workspace.zeroed:
-        raise CSError("beam_decode_step needs a Workspace(zeroed=True) of its own (arrival counters)")
-    ws = workspace.get(nbytes, dev)
-    if kept_out is not None:
-        if (kept_out.dtype != torch.float32 or not kept_out.is_contiguous()
-                or tuple(kept_out.shape) != (A, n_order)):
-            raise CSError(f"kept_out must be a contiguous float32 [{A}, {n_order}] tensor")
-        _require_cuda(kept_out)
+    U, W, order, oval = _beam_outputs(A, C, n_order, dev, out_U, out_W, kept_out, out_order)
+    workspace, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _decode_ws, int(L.cs_beam_decode_workspace_size(A, B, vocab, k)), dev,
+        "beam_decode_step")
     rc = L.cs_beam_decode_step(ref_logits.data_ptr(), ld_ref, logits.data_ptr(), ld,
                                _DTYPE[logits.dtype], A, B, vocab, k, float(softcap),
                                rewards.data_ptr(), int(kind), float(eps), ids.data_ptr(),
@@ -390,26 +396,13 @@ def beam_decode_step(ref_logits: torch.Tensor, logits: torch.Tensor, rewards: to
                                order.data_ptr() if n_order else None,
                                oval.data_ptr() if n_order else None,
                                kept_out.data_ptr() if kept_out is not None else None,
-                               ws.data_ptr(), ws.numel(), _stream())
+                               ws_ptr, ws_bytes, _stream())
     if rc != 0:
         workspace.reset()
     _lib.check(rc, "cs_beam_decode_step")
     if n_order == 0:
         return ids, U, W, None, None
     return ids, U, W, order, oval
-
-
-def _logits_args(logits: torch.Tensor, vocab: Optional[int]):
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise CSError("logits must be 2-D with unit column stride")
-    if logits.dtype not in _DTYPE:
-        raise CSError(f"unsupported logits dtype {logits.dtype}")
-    rows = logits.shape[0]
-    ld = logits.stride(0) if rows > 1 else logits.shape[1]
-    vocab = logits.shape[1] if vocab is None else int(vocab)
-    if vocab > logits.shape[1]:
-        raise CSError("vocab exceeds logits width")
-    return rows, ld, vocab
 
 
 def vocab_topk(logits: torch.Tensor, k: int, *, vocab: Optional[int] = None, softcap: float = 0.0,
@@ -422,14 +415,11 @@ def vocab_topk(logits: torch.Tensor, k: int, *, vocab: Optional[int] = None, sof
     _require_cuda(logits)
     ids = torch.empty((rows, k), dtype=torch.int32, device=logits.device)
     vals = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
-    nbytes = int(L.cs_vocab_topk_workspace_size(rows, vocab, k))
-    if workspace is None:
-        workspace = _default_ws.setdefault(logits.device, Workspace())
-    ws = workspace.get(nbytes, logits.device)
+    _, ws_ptr, ws_bytes = _workspace_args(workspace, _default_ws,
+                                          int(L.cs_vocab_topk_workspace_size(rows, vocab, k)),
+                                          logits.device)
     rc = L.cs_vocab_topk(logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld, int(k),
-                         float(softcap), ids.data_ptr(), vals.data_ptr(),
-                         ws.data_ptr() if ws is not None else None,
-                         ws.numel() if ws is not None else 0, _stream())
+                         float(softcap), ids.data_ptr(), vals.data_ptr(), ws_ptr, ws_bytes, _stream())
     _lib.check(rc, "cs_vocab_topk")
     return ids, vals
 
@@ -448,14 +438,12 @@ def vocab_sample(logits: torch.Tensor, seeds: torch.Tensor, *, temperature: floa
     n_draw = seeds.shape[1]
     ids = torch.empty((rows, n_draw), dtype=torch.int32, device=logits.device)
     lp = torch.empty((rows, n_draw), dtype=torch.float32, device=logits.device)
-    nbytes = int(L.cs_vocab_sample_workspace_size(rows, vocab, n_draw))
-    if workspace is None:
-        workspace = _default_ws.setdefault(logits.device, Workspace())
-    ws = workspace.get(nbytes, logits.device)
+    _, ws_ptr, ws_bytes = _workspace_args(workspace, _default_ws,
+                                          int(L.cs_vocab_sample_workspace_size(rows, vocab, n_draw)),
+                                          logits.device)
     rc = L.cs_vocab_sample(logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld,
                            float(temperature), float(softcap), seeds.data_ptr(), n_draw,
-                           ids.data_ptr(), lp.data_ptr(), ws.data_ptr() if ws is not None else None,
-                           ws.numel() if ws is not None else 0, _stream())
+                           ids.data_ptr(), lp.data_ptr(), ws_ptr, ws_bytes, _stream())
     _lib.check(rc, "cs_vocab_sample")
     return ids, lp
 

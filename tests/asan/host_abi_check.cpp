@@ -235,6 +235,286 @@ static void check_rejections() {
 }
 
 // ---------------------------------------------------------------------------------------
+// The five vocab-stream entry points (cs_logsoftmax_gather, cs_vocab_topk, cs_vocab_sample,
+// cs_beam_step, cs_beam_decode_step): one violated condition per row and the exact status,
+// the accept-without-launch cases, and the workspace sizes against the formulas restated
+// in `today` below.  Every call here returns before a launch.
+namespace today {
+struct Split {
+  int32_t nsplit;
+  int64_t len;
+};
+static Split plan_split(int64_t rows, int64_t vocab, int dtype) {
+  Split p{1, vocab};
+  if (rows <= 0 || vocab <= 0 || rows >= 256) return p;
+  const int64_t grain = 256 * (dtype == CS_F32 ? 4 : 8), min_len = grain * 4;
+  int64_t want = (256 * 4 + rows - 1) / rows;
+  const int64_t max_split = std::max<int64_t>(vocab / min_len, 1);
+  want = std::min(want, max_split);
+  if (want <= 1) return p;
+  int64_t len = (vocab + want - 1) / want;
+  len = (len + grain - 1) / grain * grain;
+  const int32_t ns = static_cast<int32_t>((vocab + len - 1) / len);
+  return ns <= 1 ? p : Split{ns, len};
+}
+static int64_t pad_line(int64_t n, int64_t elt_bytes) { return (n * elt_bytes + 127) / 128 * 128 / elt_bytes; }
+constexpr size_t kCounters = 64 + 4 * 65536 + 4 * 16384;   // done | row counters | welfare keys
+static size_t lsg_need(int64_t rows, int64_t vocab, int dtype) {
+  const int32_t ns = plan_split(rows, vocab, dtype).nsplit;
+  return ns <= 1 ? 0 : static_cast<size_t>(rows) * ns * 8;
+}
+static size_t beam_need(int64_t rows, int64_t vocab, int dtype) {
+  return kCounters + static_cast<size_t>(rows) * pad_line(plan_split(rows, vocab, dtype).nsplit, 8) * 8;
+}
+static size_t topk_need(int64_t rows, int64_t vocab, int32_t k) {
+  return static_cast<size_t>(rows) * ((vocab + 4095) / 4096) * k * 8;
+}
+static size_t sample_need(int64_t rows, int64_t vocab, int32_t n_draw) {
+  return static_cast<size_t>(rows) * plan_split(rows, vocab, CS_F32).nsplit * (8 + n_draw * 8);
+}
+static size_t decode_need(int32_t A, int32_t B, int64_t vocab, int32_t K, int dtype) {
+  const int64_t rows = static_cast<int64_t>(A) * B;
+  const int big = dtype != CS_F32 ? 16 : 8;
+  const int64_t nbig = B * ((vocab + big * 1024 - 1) / (big * 1024));
+  const int64_t n4c = (vocab + 4095) / 4096;
+  const int kp = (nbig < 128 && n4c * K <= 16384) ? 4 : big;
+  const int64_t nchunk = (vocab + kp * 1024 - 1) / (kp * 1024);
+  return kCounters + 2 * 4 * 4096 + 4 * static_cast<size_t>(B) * pad_line(A, 4) +
+         4 * static_cast<size_t>(B) * pad_line(K, 4) + 8 * static_cast<size_t>(B) * pad_line(nchunk * K, 8) +
+         8 * static_cast<size_t>(rows) * pad_line(plan_split(rows, vocab, dtype).nsplit, 8);
+}
+}  // namespace today
+
+static void* const kD = reinterpret_cast<void*>(uintptr_t{256});   // never dereferenced
+static float* const kF = reinterpret_cast<float*>(uintptr_t{256});
+static int32_t* const kI = reinterpret_cast<int32_t*>(uintptr_t{256});
+static void* const kOdd = reinterpret_cast<void*>(uintptr_t{257});   // not 2-byte aligned
+static void* const kOff4 = reinterpret_cast<void*>(uintptr_t{260});  // 4- but not 8-byte aligned
+
+// A valid call of each entry point as a struct of its arguments; a table row changes one.
+struct Lsg {
+  static constexpr const char* name = "cs_logsoftmax_gather";
+  const void* logits = kD; int dtype = CS_F32; int64_t rows = 4, vocab = 128, ld = 128;
+  const int32_t* tgt = kI; int32_t k = 1; float cap = 0.f; float* out = kF;
+  void* ws = kD; size_t wsb = 1 << 20;
+  int call() const {
+    return cs_logsoftmax_gather(logits, dtype, rows, vocab, ld, tgt, k, cap, out, nullptr, ws, wsb, nullptr);
+  }
+  void split_rows() { vocab = ld = 128256; wsb = need(); }   // rows that need the workspace
+  size_t need() const { return today::lsg_need(rows, vocab, dtype); }
+};
+struct Topk {
+  static constexpr const char* name = "cs_vocab_topk";
+  const void* logits = kD; int dtype = CS_F32; int64_t rows = 2, vocab = 128, ld = 128;
+  int32_t k = 4; float cap = 0.f; int32_t* ids = kI; void* ws = kD; size_t wsb = 1 << 20;
+  int call() const {
+    return cs_vocab_topk(logits, dtype, rows, vocab, ld, k, cap, ids, nullptr, ws, wsb, nullptr);
+  }
+  void split_rows() { wsb = need(); }
+  size_t need() const { return today::topk_need(rows, vocab, k); }
+};
+struct Sample {
+  static constexpr const char* name = "cs_vocab_sample";
+  const void* logits = kD; int dtype = CS_F32; int64_t rows = 2, vocab = 128, ld = 128;
+  float temp = 1.f, cap = 0.f; const uint64_t* seeds = reinterpret_cast<const uint64_t*>(kD);
+  int32_t n_draw = 1; int32_t* ids = kI; void* ws = kD; size_t wsb = 1 << 20;
+  int call() const {
+    return cs_vocab_sample(logits, dtype, rows, vocab, ld, temp, cap, seeds, n_draw, ids, nullptr, ws, wsb, nullptr);
+  }
+  void split_rows() { wsb = need(); }
+  size_t need() const { return today::sample_need(rows, vocab, n_draw); }
+};
+struct Step {
+  static constexpr const char* name = "cs_beam_step";
+  const void* logits = kD; int dtype = CS_F32; int32_t A = 2, B = 2; int64_t vocab = 128, ld = 128;
+  const int32_t* tgt = kI; int32_t K = 4; const float* R = kF; float cap = 0.f; int kind = CS_WELFARE_MIN;
+  float* U = kF; float* W = kF; int32_t n_order = 0; int32_t* order = nullptr; float* kept = nullptr;
+  void* ws = kD; size_t wsb = 1 << 20;
+  int call() const {
+    return cs_beam_step(logits, dtype, A, B, vocab, ld, tgt, K, R, cap, kind, 1e-9f, U, W, n_order, order,
+                        nullptr, kept, ws, wsb, nullptr);
+  }
+  void split_rows() { vocab = ld = 128256; wsb = need(); }
+  size_t need() const { return today::beam_need(static_cast<int64_t>(A) * B, vocab, dtype); }
+};
+struct Decode {
+  static constexpr const char* name = "cs_beam_decode_step";
+  const void* ref = kD; int64_t ld_ref = 128; const void* logits = kD; int64_t ld = 128; int dtype = CS_F32;
+  int32_t A = 2, B = 2; int64_t vocab = 128; int32_t K = 4; float cap = 0.f; const float* R = kF;
+  int kind = CS_WELFARE_MIN; int32_t* ids = kI; float* U = kF; float* W = kF; int32_t n_order = 0;
+  int32_t* order = nullptr; float* kept = nullptr; void* ws = kD; size_t wsb = 1 << 20;
+  int call() const {
+    return cs_beam_decode_step(ref, ld_ref, logits, ld, dtype, A, B, vocab, K, cap, R, kind, 1e-9f, ids, U, W,
+                               n_order, order, nullptr, kept, ws, wsb, nullptr);
+  }
+  void split_rows() { vocab = ld = ld_ref = 128256; wsb = need(); }
+  size_t need() const { return today::decode_need(A, B, vocab, K, dtype); }
+};
+
+// one table row: entry point T with `change` applied to a valid call returns exactly `code`
+// and leaves a message that names the entry point
+#define REJECTS_WITH(T, change, code)                                                         \
+  do {                                                                                        \
+    T a;                                                                                      \
+    change;                                                                                   \
+    const int rc_ = a.call();                                                                 \
+    CHECK(rc_ == (code) && std::strstr(cs_last_error(), T::name) != nullptr,                   \
+          "%s { %s }: status %d, want %d (%s)", T::name, #change, rc_, (code), cs_last_error()); \
+  } while (0)
+#define ACCEPTS(T, change)                                                        \
+  do {                                                                            \
+    T a;                                                                          \
+    change;                                                                       \
+    const int rc_ = a.call();                                                     \
+    CHECK(rc_ == CS_OK, "%s { %s }: status %d, want 0", T::name, #change, rc_);   \
+  } while (0)
+
+// the conditions every one of the five checks
+template <typename T>
+static void stream_common_rows() {
+  REJECTS_WITH(T, a.dtype = 7, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.dtype = -1, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.ld = a.vocab - 1, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.vocab = 0, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.vocab = -5, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.cap = -1.f, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.cap = INFINITY, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.cap = -INFINITY, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.cap = NAN, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.logits = nullptr, CS_ERR_INVALID);
+  // the workspace: missing, one byte short of this dtype's need
+  for (int dt : {CS_F32, CS_BF16, CS_F16}) {
+    REJECTS_WITH(T, (a.dtype = dt, a.split_rows(), a.ws = nullptr), CS_ERR_WORKSPACE);
+    REJECTS_WITH(T, (a.dtype = dt, a.split_rows(), a.ws = nullptr, a.wsb = 0), CS_ERR_WORKSPACE);
+    REJECTS_WITH(T, (a.dtype = dt, a.split_rows(), a.wsb -= 1), CS_ERR_WORKSPACE);
+  }
+}
+// a workspace that is 4- but not 8-byte aligned
+template <typename T>
+static void workspace_alignment_rows() {
+  REJECTS_WITH(T, (a.split_rows(), a.ws = kOff4, a.wsb = 1 << 24), CS_ERR_WORKSPACE);
+}
+// 16-bit logits at an odd address
+template <typename T>
+static void element_alignment_rows() {
+  REJECTS_WITH(T, (a.dtype = CS_BF16, a.logits = kOdd), CS_ERR_INVALID);
+  REJECTS_WITH(T, (a.dtype = CS_F16, a.logits = kOdd), CS_ERR_INVALID);
+}
+// the limits the two beam entry points share
+template <typename T>
+static void beam_common_rows() {
+  REJECTS_WITH(T, a.R = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.U = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.W = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.n_order = 1, CS_ERR_INVALID);                      // out_order is NULL
+  REJECTS_WITH(T, (a.n_order = 9, a.order = kI), CS_ERR_INVALID);      // B*K = 8
+  REJECTS_WITH(T, (a.n_order = -1, a.order = kI), CS_ERR_INVALID);
+  REJECTS_WITH(T, a.kept = kF, CS_ERR_INVALID);                        // out_kept with n_order = 0
+  REJECTS_WITH(T, (a.B = 41, a.K = 25, a.n_order = 1, a.order = kI, a.kept = kF), CS_ERR_INVALID);  // 1025
+  REJECTS_WITH(T, (a.B = 565, a.K = 29), CS_ERR_INVALID);              // B*K = 16385
+  REJECTS_WITH(T, (a.A = 65537, a.B = 1), CS_ERR_INVALID);             // A*B = 65537
+  REJECTS_WITH(T, a.kind = -1, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.kind = 4, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.A = -1, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.B = -1, CS_ERR_INVALID);
+  REJECTS_WITH(T, a.K = -1, CS_ERR_INVALID);
+}
+
+static void check_stream_family(std::mt19937_64& rng) {
+  stream_common_rows<Lsg>();
+  stream_common_rows<Topk>();
+  stream_common_rows<Sample>();
+  stream_common_rows<Step>();
+  stream_common_rows<Decode>();
+  workspace_alignment_rows<Lsg>();
+  workspace_alignment_rows<Sample>();
+  workspace_alignment_rows<Step>();
+  workspace_alignment_rows<Decode>();
+  element_alignment_rows<Lsg>();
+  element_alignment_rows<Step>();
+  element_alignment_rows<Decode>();
+  REJECTS_WITH(Decode, (a.dtype = CS_BF16, a.ref = kOdd), CS_ERR_INVALID);
+  beam_common_rows<Step>();
+  beam_common_rows<Decode>();
+
+  REJECTS_WITH(Lsg, a.rows = -1, CS_ERR_INVALID);
+  REJECTS_WITH(Lsg, a.rows = int64_t{1} << 31, CS_ERR_INVALID);
+  REJECTS_WITH(Lsg, a.k = -1, CS_ERR_INVALID);
+  REJECTS_WITH(Lsg, a.tgt = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(Lsg, a.out = nullptr, CS_ERR_INVALID);
+  ACCEPTS(Lsg, a.rows = 0);
+  ACCEPTS(Lsg, (a.rows = 0, a.logits = nullptr, a.ws = nullptr, a.wsb = 0));
+
+  REJECTS_WITH(Topk, a.rows = -1, CS_ERR_INVALID);
+  REJECTS_WITH(Topk, a.k = 0, CS_ERR_INVALID);
+  REJECTS_WITH(Topk, a.k = -3, CS_ERR_INVALID);
+  REJECTS_WITH(Topk, a.k = 129, CS_ERR_INVALID);                          // > vocab
+  REJECTS_WITH(Topk, (a.vocab = a.ld = 1000, a.k = 257), CS_ERR_INVALID);   // > 256
+  REJECTS_WITH(Topk, a.ids = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(Topk, (a.vocab = a.ld = 4096 * 65, a.k = 256), CS_ERR_INVALID);   // chunks x k > 16384
+  ACCEPTS(Topk, a.rows = 0);
+
+  REJECTS_WITH(Sample, a.rows = -1, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.n_draw = 0, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.n_draw = 17, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.temp = 0.f, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.temp = -1.f, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.temp = INFINITY, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.temp = NAN, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.seeds = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(Sample, a.ids = nullptr, CS_ERR_INVALID);
+  ACCEPTS(Sample, a.rows = 0);
+
+  REJECTS_WITH(Step, a.tgt = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(Step, a.A = 0, CS_ERR_INVALID);                 // no agents but candidates
+  REJECTS_WITH(Step, (a.B = 1, a.K = 16385), CS_ERR_INVALID);
+  REJECTS_WITH(Step, (a.B = 1, a.K = 1025, a.n_order = 1, a.order = kI, a.kept = kF), CS_ERR_INVALID);
+  ACCEPTS(Step, a.K = 0);                                      // C == 0
+  ACCEPTS(Step, a.B = 0);
+  ACCEPTS(Step, (a.A = 0, a.K = 0));
+  ACCEPTS(Step, (a.K = 0, a.logits = nullptr, a.ws = nullptr, a.wsb = 0));
+
+  REJECTS_WITH(Decode, a.ref = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(Decode, a.ids = nullptr, CS_ERR_INVALID);
+  REJECTS_WITH(Decode, a.ld_ref = 127, CS_ERR_INVALID);
+  REJECTS_WITH(Decode, a.A = 0, CS_ERR_INVALID);
+  REJECTS_WITH(Decode, a.B = 0, CS_ERR_INVALID);
+  REJECTS_WITH(Decode, a.K = 0, CS_ERR_INVALID);
+  REJECTS_WITH(Decode, a.K = 129, CS_ERR_INVALID);                             // > vocab
+  REJECTS_WITH(Decode, (a.vocab = a.ld = a.ld_ref = 1000, a.K = 257), CS_ERR_INVALID);
+  REJECTS_WITH(Decode, (a.B = 4097, a.K = 3), CS_ERR_INVALID);                 // B*K and A*B in range
+
+  // workspace sizes: the library's against the restated formulas
+  for (int it = 0; it < 200; ++it) {
+    const int32_t A = 1 + static_cast<int32_t>(rng() % 70), B = 1 + static_cast<int32_t>(rng() % 20);
+    const int64_t rows = (it % 3 == 0) ? 1 + static_cast<int64_t>(rng() % 3000) : static_cast<int64_t>(A) * B;
+    const int64_t V = (it % 5 == 0) ? 1 + static_cast<int64_t>(rng() % 9000) : 1 + static_cast<int64_t>(rng() % 300000);
+    const int32_t K = 1 + static_cast<int32_t>(rng() % 256), nd = 1 + static_cast<int32_t>(rng() % 16);
+    CHECK(cs_workspace_size(rows, V, K) == std::max(today::lsg_need(rows, V, CS_BF16), today::lsg_need(rows, V, CS_F32)),
+          "cs_workspace_size(%lld, %lld)", (long long)rows, (long long)V);
+    CHECK(cs_beam_step_workspace_size(rows, V) ==
+              std::max(today::beam_need(rows, V, CS_BF16), today::beam_need(rows, V, CS_F32)),
+          "cs_beam_step_workspace_size(%lld, %lld)", (long long)rows, (long long)V);
+    CHECK(cs_vocab_topk_workspace_size(rows, V, K) == today::topk_need(rows, V, K),
+          "cs_vocab_topk_workspace_size(%lld, %lld, %d)", (long long)rows, (long long)V, K);
+    CHECK(cs_vocab_sample_workspace_size(rows, V, nd) == today::sample_need(rows, V, nd),
+          "cs_vocab_sample_workspace_size(%lld, %lld, %d)", (long long)rows, (long long)V, nd);
+    CHECK(cs_beam_decode_workspace_size(A, B, V, K) ==
+              std::max(today::decode_need(A, B, V, K, CS_BF16), today::decode_need(A, B, V, K, CS_F32)),
+          "cs_beam_decode_workspace_size(%d, %d, %lld, %d)", A, B, (long long)V, K);
+  }
+  for (int64_t z : {int64_t{0}, int64_t{-1}}) {
+    CHECK(cs_beam_step_workspace_size(z, 1000) == 0 && cs_beam_step_workspace_size(4, z) == 0, "empty beam size");
+    CHECK(cs_vocab_topk_workspace_size(z, 1000, 4) == 0 && cs_vocab_topk_workspace_size(4, z, 4) == 0 &&
+              cs_vocab_topk_workspace_size(4, 1000, static_cast<int32_t>(z)) == 0, "empty top-k size");
+    CHECK(cs_vocab_sample_workspace_size(z, 1000, 4) == 0 && cs_vocab_sample_workspace_size(4, z, 4) == 0 &&
+              cs_vocab_sample_workspace_size(4, 1000, static_cast<int32_t>(z)) == 0, "empty sample size");
+    CHECK(cs_beam_decode_workspace_size(static_cast<int32_t>(z), 2, 1000, 4) == 0 &&
+              cs_beam_decode_workspace_size(2, 2, z, 4) == 0, "empty decode size");
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // the C oracle under the sanitizers: known answers from a direct fp64 restatement
 static uint16_t to_bf16(float x) {
   uint32_t u;
@@ -332,6 +612,7 @@ int main(int argc, char** argv) {
   check_planners(rng, iters);
   check_rejections();
   check_oracle(rng);
+  check_stream_family(rng);
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

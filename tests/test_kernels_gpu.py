@@ -682,3 +682,120 @@ def test_beam_decode_fuzz(ops, orc, dev, i, dtype, A, B, K, vocab, softcap, kind
     assert torch.equal(on, o[:n])
     if kept is not None:
         assert torch.equal(kept, U[:, on.long()])
+
+
+# --- every compiled instantiation of the two beam kernels, and cs_beam_step with K > 1024 ---
+def _eq_nan(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return torch.equal(torch.nan_to_num(a, nan=7.0), torch.nan_to_num(b, nan=7.0))
+
+
+def _plan_nsplit(rows: int, vocab: int, dtype) -> int:
+    """The library's split plan (cs_kernels.cuh plan_split), restated on the CPU."""
+    if rows >= 256:
+        return 1
+    grain = 256 * (4 if dtype == torch.float32 else 8)
+    want = min((1024 + rows - 1) // rows, max(vocab // (grain * 4), 1))
+    if want <= 1:
+        return 1
+    length = -(-(-(-vocab // want)) // grain) * grain
+    return max(-(-vocab // length), 1)
+
+
+def _decode_kp(B: int, vocab: int, K: int, dtype) -> int:
+    """Elements per lane of a proposer chunk (beam.hip decode_kp), restated on the CPU."""
+    big = 8 if dtype == torch.float32 else 16
+    nbig = B * -(-vocab // (big * 1024))
+    return 4 if nbig < 128 and -(-vocab // 4096) * K <= 16384 else big
+
+
+def _check_beam_step_is_unfused(ops, lg, tg, Rg, kind, softcap):
+    """cs_beam_step == cs_logsoftmax_gather + cs_welfare_reduce + cs_segmented_topk, bit for bit."""
+    A, B = Rg.shape
+    K = tg.shape[1]
+    U, W, order, oval = ops.beam_step(lg, tg, Rg, kind, softcap=softcap)
+    tok, _ = ops.logsoftmax_gather(lg, tg.repeat(A, 1), softcap=softcap)
+    U2 = (Rg[:, :, None] + tok.view(A, B, K)).reshape(A, B * K).contiguous()
+    W2 = ops.welfare(U2, kind)
+    o2, v2 = ops.topk(W2, B * K)
+    assert _eq_nan(U, U2) and _eq_nan(W, W2)
+    assert torch.equal(order, o2) and _eq_nan(oval, v2)
+    return U, W, order, tok
+
+
+def _check_lsg_oracle(orc, logits_cpu, tgt_rows, tok, softcap, vocab):
+    host, bf16 = _host_logits(logits_cpu)
+    o_tok, _ = orc.logsoftmax_gather(np.ascontiguousarray(host), tgt_rows.numpy(), softcap=softcap,
+                                     bf16=bf16, vocab=vocab)
+    t = tok.cpu().numpy()
+    assert np.array_equal(np.isnan(t), np.isnan(o_tok))
+    assert np.nanmax(np.abs(t - o_tok)) < LP_TOL
+
+
+BEAM_INST_SHAPES = {
+    # name: (A, B, K, vocab(dtype), kind, nsplit fp32 / 16-bit, proposer keys per lane fp32 / 16-bit)
+    "split": (3, 2, 5, lambda dt: 50000, "min", (10, 5), (4, 4)),       # partial quads of 2 and 1
+    "unsplit": (32, 8, 3, lambda dt: 1031, "sum", (1, 1), (4, 4)),      # 256 rows, single pass
+    # the first vocab with 16 x 8 = 128 proposer workgroups at 8 / 16 keys per lane
+    "bigchunk": (1, 16, 3, lambda dt: 57345 if dt == torch.float32 else 114689, "min", None, (8, 16)),
+}
+
+
+@pytest.mark.parametrize("shape", list(BEAM_INST_SHAPES))
+@pytest.mark.parametrize("softcap", [0.0, 30.0, 75.0])   # no cap, fixed-offset cap, general cap
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_beam_kernels_every_instantiation(ops, orc, dev, dtype, softcap, shape):
+    """dtype x {no cap, cap <= 60, cap > 60} x {split rows, unsplit rows} for cs_beam_step and
+    x {4, 8 / 16 proposer keys per lane} for cs_beam_decode_step: each compiled beam kernel once.
+    beam_step == logsoftmax_gather + welfare + topk and beam_decode_step == vocab_topk +
+    beam_step bit for bit; logsoftmax_gather within LP_TOL of the CPU oracle."""
+    A, B, K, vfn, kind, nsplit, kp = BEAM_INST_SHAPES[shape]
+    vocab = vfn(dtype)
+    f32 = dtype == torch.float32
+    if nsplit is not None:
+        assert _plan_nsplit(A * B, vocab, dtype) == nsplit[0 if f32 else 1]
+    assert _decode_kp(B, vocab, K, dtype) == kp[0 if f32 else 1]
+    g = torch.Generator().manual_seed(A * 131 + B * 7 + K + vocab)
+    # logits up to ~ +-100: past the general cap of 75, far past the fixed-offset cap of 30
+    logits = (torch.randn(A * B, vocab, generator=g) * 25.0).to(dtype)
+    ref = (torch.randn(B, vocab, generator=g) * 25.0).to(dtype)
+    tgt = torch.randint(0, vocab, (B, K), generator=g, dtype=torch.int32)
+    tgt[B - 1, K - 1] = -1
+    tgt[0, 0] = tgt[0, 1]
+    R = -torch.rand(A, B, generator=g) * 20.0
+    lg, rg, tg, Rg = logits.to(dev), ref.to(dev), tgt.to(dev), R.to(dev)
+    if shape != "bigchunk":
+        _, _, _, tok = _check_beam_step_is_unfused(ops, lg, tg, Rg, kind, softcap)
+        _check_lsg_oracle(orc, logits, tgt.repeat(A, 1), tok, softcap, vocab)
+    ids, _ = ops.vocab_topk(rg, K, softcap=softcap)
+    U, W, o, tok = _check_beam_step_is_unfused(ops, lg, ids, Rg, kind, softcap)
+    _check_lsg_oracle(orc, logits, ids.cpu().repeat(A, 1), tok, softcap, vocab)
+    for rep in range(2):   # the workspace is reused (counters left at zero)
+        ids2, U2, W2, o2, _ = ops.beam_decode_step(rg, lg, Rg, K, kind, softcap=softcap)
+        assert torch.equal(ids, ids2)
+        assert _eq_nan(U, U2) and _eq_nan(W, W2)
+        assert torch.equal(o, o2)
+    kept = torch.empty(A, B, device=dev)
+    _, _, _, on, _ = ops.beam_decode_step(rg, lg, Rg, K, kind, n_order=B, softcap=softcap, kept_out=kept)
+    assert torch.equal(on, o[:B]) and _eq_nan(kept, U[:, on.long()])
+
+
+@pytest.mark.parametrize("kind", ["min", "sum"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("A,B,K,vocab", [(2, 1, 1500, 3001), (2, 2, 1100, 3001)])
+def test_beam_step_more_candidates_per_beam_than_threads(ops, orc, dev, A, B, K, vocab, dtype, kind):
+    """K > 1024: the row finisher's gather loops past its early read, and B*K > 1024 is sorted
+    after the launch.  Bit-identical to the unfused kernels, in the oracle's stable order."""
+    g = torch.Generator().manual_seed(A * 131 + B * 7 + K)
+    logits = (torch.randn(A * B, vocab, generator=g) * 3.0).to(dtype)
+    tgt = torch.randint(0, vocab, (B, K), generator=g, dtype=torch.int32)
+    tgt[0, 3] = tgt[0, 1030] = tgt[B - 1, K - 1] = -1          # padding on both sides of 1024
+    tgt[0, 5] = tgt[0, 1029] = tgt[0, 1028] = tgt[0, 4]        # duplicates across it
+    tgt[B - 1, 1024] = vocab                                   # out of range
+    R = -torch.rand(A, B, generator=g) * 20.0
+    lg, tg, Rg = logits.to(dev), tgt.to(dev), R.to(dev)
+    U, W, order, tok = _check_beam_step_is_unfused(ops, lg, tg, Rg, kind, softcap=0.0)
+    _check_lsg_oracle(orc, logits, tgt.repeat(A, 1), tok, 0.0, vocab)
+    assert np.array_equal(order.cpu().numpy(), orc.topk(W.cpu().numpy().astype(np.float64), B * K)[0])
+    for n in (1, 300):   # partial orders are the full order's prefix
+        _, _, on, _ = ops.beam_step(lg, tg, Rg, kind, n_order=n)
+        assert torch.equal(on, order[:n])
