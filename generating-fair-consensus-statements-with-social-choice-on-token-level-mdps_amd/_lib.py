@@ -30,7 +30,7 @@ EXPORTED = (
     "cs_gemm_bf16", "cs_gemm_splits",
     "cs_gemm_bf16_packed", "cs_gemm_pack", "cs_rope_place_splitk",
     "cs_add_rms_norm_splitk", "cs_prefix_attention_rows", "cs_rope_place_rows",
-    "cs_rope_place_splitk_rows", "cs_hist_rows_update",
+    "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
 )
 
 
@@ -147,6 +147,11 @@ def load():
     L.cs_rope_place_splitk_rows.restype = ctypes.c_int
     L.cs_hist_rows_update.argtypes = [vp, vp, vp, vp, i64, i32, i64, i64, vp]
     L.cs_hist_rows_update.restype = ctypes.c_int
+    L.cs_nash_lottery.argtypes = [vp, i32, i32, i32, i64, i64, i32, ctypes.c_double, ctypes.c_int,
+                                  vp, vp, vp, vp, vp, vp]
+    L.cs_nash_lottery.restype = ctypes.c_int
+    L.cs_lottery_policy.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.cs_lottery_policy.restype = ctypes.c_int
     _lib = L
     return L
 

@@ -1,0 +1,390 @@
+// lottery.hip — the Nash-welfare lottery over complete statements and the token policy it
+// induces (the reference's core.py:116-168 and 297-328), whole solves in one launch.
+#include "cs_kernels.cuh"
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// cs_nash_lottery: Frank-Wolfe with a golden-section line search, one workgroup per problem
+// ---------------------------------------------------------------------------
+// Per iteration (core.py:125-166), fp64 throughout:
+//   1. every thread takes the columns j = tid, tid + BLOCK, ...: g_j = sum_i U[i,j] / a_i over
+//      the agents in index order, and keeps its best (g, j), the lowest j on ties;
+//   2. the block's best (wave butterfly, then the waves' bests through LDS) is j*: the pair
+//      order (g desc, j asc) is total, so the result does not depend on how it is reduced;
+//   3. wave 0, one lane per agent, runs the line search on F(gamma) = sum_i log((1 - gamma) a_i
+//      + gamma U[i,j*]): each evaluation is one log per lane and a butterfly sum whose value
+//      lane 0 broadcasts, so the bracket updates are wave-uniform; it then carries
+//      a <- (1 - gamma*) a + gamma* U[:,j*] and F_new = sum_i log a_i;
+//   4. every thread rescales its own columns of p (held in out_p, nobody else touches them).
+// The STAGED variant keeps the problem's U in LDS ([A][m], the global layout with ld = m) and
+// differs from the global one only in where a U value is loaded from: the arithmetic and its
+// order are the same, so the outputs are bitwise equal.  No atomics, no host sync.
+// After the last iteration a = U p is recomputed from the returned p (one wave per agent row, a
+// fixed lane-strided order), so a, F and gap = max_j g_j - A are the certificate of exactly the
+// p written.
+constexpr int kLotMaxA = 64;
+constexpr int kLotMaxM = 16384;
+constexpr int kLotMaxRounds = 80;             // core.py:142
+constexpr double kLotBracket = 1e-9;          // core.py:155
+constexpr double kGolden = 0x1.3c6ef372fe95p-1;  // (sqrt(5) - 1) / 2 in fp64, core.py:137
+// LDS the staged variant may take for U: the CU's 160 KiB less the kernel's own few hundred
+// bytes, rounded down to leave room
+constexpr size_t kLotLdsBytes = 144 * 1024;
+constexpr int kLotWideM = 4096;               // above this many columns: 1024-thread workgroups
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  return __shfl_xor(v, mask, 64);
+}
+
+// sum over the first `width` lanes (a power of two >= the lanes that hold a term; the others
+// hold 0), broadcast from lane 0: every lane returns the same bits
+__device__ __forceinline__ double wave_sum_bcast(double v, int width) {
+  for (int k = 1; k < width; k <<= 1) v += shfl_xor_f64(v, k);
+  return __shfl(v, 0, 64);
+}
+
+// (g, j) ordered by g descending, then j ascending: np.argmax's first maximum
+__device__ __forceinline__ bool lot_better(double g, int32_t j, double g0, int32_t j0) {
+  return g > g0 || (g == g0 && j < j0);
+}
+
+struct LotSmem {
+  double a[kLotMaxA];
+  double wg[16];       // one best per wave
+  int32_t wj[16];
+  double gamma, f_new;
+  int32_t jstar;
+};
+
+// a_i = sum_j U[i,j] p_j for every agent into S.a: wave w takes the rows w, w + nwaves, ...;
+// lane l adds the columns l, l + 64, ... in order, then a butterfly over the 64 lanes
+template <int BLOCK, bool STAGED>
+__device__ __forceinline__ void lot_row_dots(LotSmem& S, const double* __restrict__ Ug,
+                                             const double* smU, int32_t A, int32_t m, int64_t ldu,
+                                             const double* p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int32_t i = wave; i < A; i += BLOCK / 64) {
+    double acc = 0.0;
+    for (int32_t j = lane; j < m; j += 64) {
+      const double u = STAGED ? smU[static_cast<int64_t>(i) * m + j] : Ug[i * ldu + j];
+      acc += u * p[j];
+    }
+    for (int k = 1; k < 64; k <<= 1) acc += shfl_xor_f64(acc, k);
+    if (lane == 0) S.a[i] = acc;
+  }
+}
+
+// The block's argmax_j of g_j = sum_i U[i,j] / a_i (lowest j on ties), returned to every thread
+template <int BLOCK, bool STAGED>
+__device__ __forceinline__ void lot_gradient_argmax(LotSmem& S, const double* __restrict__ Ug,
+                                                    const double* smU, int32_t A, int32_t m,
+                                                    int64_t ldu, double& g_best, int32_t& j_best) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double bg = -INFINITY;
+  int32_t bj = 0x7fffffff;
+  for (int32_t j = tid; j < m; j += BLOCK) {
+    double g = 0.0;
+    for (int32_t i = 0; i < A; ++i) {
+      const double u = STAGED ? smU[static_cast<int64_t>(i) * m + j] : Ug[i * ldu + j];
+      g += u / S.a[i];
+    }
+    if (lot_better(g, j, bg, bj)) {
+      bg = g;
+      bj = j;
+    }
+  }
+  for (int k = 1; k < 64; k <<= 1) {
+    const double og = shfl_xor_f64(bg, k);
+    const int32_t oj = __shfl_xor(bj, k, 64);
+    if (lot_better(og, oj, bg, bj)) {
+      bg = og;
+      bj = oj;
+    }
+  }
+  if (lane == 0) {
+    S.wg[wave] = bg;
+    S.wj[wave] = bj;
+  }
+  __syncthreads();
+  bg = S.wg[0];
+  bj = S.wj[0];
+  for (int w = 1; w < BLOCK / 64; ++w) {
+    if (lot_better(S.wg[w], S.wj[w], bg, bj)) {
+      bg = S.wg[w];
+      bj = S.wj[w];
+    }
+  }
+  g_best = bg;
+  j_best = bj < m ? bj : 0;   // no column won (every g NaN): still an index inside the problem
+}
+
+template <int BLOCK, bool STAGED>
+__global__ __launch_bounds__(BLOCK) void nash_lottery_kernel(
+    const double* __restrict__ U, int32_t A, int32_t m, int64_t ldu, int64_t ldp,
+    int32_t max_iters, double tol, double* out_p, double* __restrict__ out_a,
+    double* __restrict__ out_F, double* __restrict__ out_gap, int32_t* __restrict__ out_iters) {
+  extern __shared__ __attribute__((aligned(16))) double smU[];
+  __shared__ LotSmem S;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t prob = blockIdx.x;
+  const double* Ug = U + prob * ldp;
+  double* p = out_p + prob * m;
+
+  // the problem's entries: checked, staged, and p = 1/m
+  int bad = 0;
+  const double p0 = 1.0 / static_cast<double>(m);
+  for (int32_t j = tid; j < m; j += BLOCK) {
+    for (int32_t i = 0; i < A; ++i) {
+      const double u = Ug[i * ldu + j];
+      if (!(u >= 0.0) || u == INFINITY) bad = 1;
+      if (STAGED) smU[static_cast<int64_t>(i) * m + j] = u;
+    }
+    p[j] = p0;
+  }
+  bad = __syncthreads_or(bad);
+  lot_row_dots<BLOCK, STAGED>(S, Ug, smU, A, m, ldu, p);
+  __syncthreads();
+  // an agent without any utility (or a row sum that overflowed) has no log-welfare
+  if (tid < A && !(S.a[tid] > 0.0 && S.a[tid] < INFINITY)) bad = 1;
+  bad = __syncthreads_or(bad);
+  if (bad) {  // block-uniform
+    const double nan = __builtin_nan("");
+    for (int32_t j = tid; j < m; j += BLOCK) p[j] = nan;
+    if (out_a && tid < A) out_a[prob * A + tid] = nan;
+    if (tid == 0) {
+      if (out_F) out_F[prob] = nan;
+      if (out_gap) out_gap[prob] = nan;
+      if (out_iters) out_iters[prob] = -1;
+    }
+    return;
+  }
+
+  int width = 1;  // butterfly width of the per-agent sums
+  while (width < A) width <<= 1;
+  // F_prev = F(p): sum_i log a_i (every wave computes it, all get the same bits)
+  double f_prev = wave_sum_bcast(lane < A ? log(S.a[lane]) : 0.0, width);
+  int32_t iters = 0;
+  for (int32_t it = 0; it < max_iters; ++it) {
+    double g_best;
+    int32_t jstar;
+    lot_gradient_argmax<BLOCK, STAGED>(S, Ug, smU, A, m, ldu, g_best, jstar);
+    if (tid < 64) {
+      const bool on = lane < A;
+      const double a = on ? S.a[lane] : 1.0;
+      const double b = on ? (STAGED ? smU[static_cast<int64_t>(lane) * m + jstar]
+                                    : Ug[lane * ldu + jstar])
+                          : 1.0;
+      auto f_gamma = [&](double gamma) {
+        const double x = (1.0 - gamma) * a + gamma * b;
+        return wave_sum_bcast(on ? log(x) : 0.0, width);
+      };
+      double lo = 0.0, hi = 1.0;
+      double c = hi - kGolden * (hi - lo);
+      double d = lo + kGolden * (hi - lo);
+      double fc = f_gamma(c);
+      double fd = f_gamma(d);
+      for (int r = 0; r < kLotMaxRounds; ++r) {
+        if (fc < fd) {
+          lo = c;
+          c = d;
+          fc = fd;
+          d = lo + kGolden * (hi - lo);
+          fd = f_gamma(d);
+        } else {
+          hi = d;
+          d = c;
+          fd = fc;
+          c = hi - kGolden * (hi - lo);
+          fc = f_gamma(c);
+        }
+        if (hi - lo < kLotBracket) break;
+      }
+      const double gamma = 0.5 * (lo + hi);
+      const double a_new = (1.0 - gamma) * a + gamma * b;
+      const double f_new = wave_sum_bcast(on ? log(a_new) : 0.0, width);
+      if (on) S.a[lane] = a_new;
+      if (lane == 0) {
+        S.gamma = gamma;
+        S.f_new = f_new;
+      }
+    }
+    __syncthreads();
+    const double gamma = S.gamma;
+    const double f_new = S.f_new;
+    for (int32_t j = tid; j < m; j += BLOCK) {
+      double pj = (1.0 - gamma) * p[j];
+      if (j == jstar) pj += gamma;
+      p[j] = pj;
+    }
+    iters = it + 1;
+    if (f_new - f_prev < tol) break;  // block-uniform; the new p is adopted first (core.py:162-164)
+    f_prev = f_new;
+  }
+
+  // the certificate of the p written: a = U p, F = sum log a, gap = max_j g_j - A
+  __syncthreads();
+  lot_row_dots<BLOCK, STAGED>(S, Ug, smU, A, m, ldu, p);
+  __syncthreads();
+  if (out_a && tid < A) out_a[prob * A + tid] = S.a[tid];
+  if (out_F) {
+    const double f = wave_sum_bcast(lane < A ? log(S.a[lane]) : 0.0, width);
+    if (tid == 0) out_F[prob] = f;
+  }
+  if (out_gap) {
+    double g_best;
+    int32_t jstar;
+    lot_gradient_argmax<BLOCK, STAGED>(S, Ug, smU, A, m, ldu, g_best, jstar);
+    if (tid == 0) out_gap[prob] = g_best - static_cast<double>(A);
+  }
+  if (out_iters && tid == 0) out_iters[prob] = iters;
+}
+
+template <int BLOCK, bool STAGED>
+void launch_lottery(hipStream_t st, int32_t P, size_t lds, const double* U, int32_t A, int32_t m,
+                    int64_t ldu, int64_t ldp, int32_t max_iters, double tol, double* out_p,
+                    double* out_a, double* out_F, double* out_gap, int32_t* out_iters) {
+  if (STAGED && lds > 64 * 1024) {
+    // more dynamic LDS than the default launch limit: raised once per process
+    static const hipError_t raised = hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&nash_lottery_kernel<BLOCK, STAGED>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLotLdsBytes));
+    (void)raised;  // a refusal shows as the launch's own error
+  }
+  hipLaunchKernelGGL((nash_lottery_kernel<BLOCK, STAGED>), dim3(P), dim3(BLOCK), lds, st, U, A, m, ldu,
+                     ldp, max_iters, tol, out_p, out_a, out_F, out_gap, out_iters);
+}
+
+// ---------------------------------------------------------------------------
+// cs_lottery_policy: prefix masses bottom-up, then pi(b | s) = mass(s + b) / mass(s)
+// ---------------------------------------------------------------------------
+// The output's level-t block (B^t entries, t = 1..L) is indexed by the length-t prefix s + b, so
+// it first holds that prefix's mass: level L is p itself, level t the sum of its B children in
+// level t + 1, in action order (one thread per parent).  The levels are then divided by their
+// parents' masses from the deepest up, each level reading the still undivided level above it;
+// level 1 divides by the root mass.  A parent of mass <= 0 gives its B actions 1/B
+// (core.py:316-320).  Every value is written by one thread in a fixed order: deterministic.
+constexpr int kPolicyBlock = 256;
+constexpr int kPolicyMaxL = 64;   // binds only at B = 1: B >= 2 has L <= 14 at the leaf limit
+
+__global__ __launch_bounds__(kPolicyBlock) void lottery_policy_kernel(
+    const double* __restrict__ p, int32_t B, int32_t L, int32_t m, int32_t total,
+    double* __restrict__ out) {
+  __shared__ int32_t off[kPolicyMaxL + 2];   // off[t]: start of level t (t = 1..L), off[L+1] = total
+  __shared__ double root;
+  const int tid = threadIdx.x;
+  const double* pp = p + static_cast<int64_t>(blockIdx.x) * m;
+  double* o = out + static_cast<int64_t>(blockIdx.x) * total;
+  if (tid == 0) {
+    int32_t at = 0, n = 1;
+    for (int32_t t = 1; t <= L; ++t) {
+      n *= B;
+      off[t] = at;
+      at += n;
+    }
+    off[L + 1] = at;
+  }
+  __syncthreads();
+  for (int32_t j = tid; j < m; j += kPolicyBlock) o[off[L] + j] = pp[j];
+  for (int32_t t = L - 1; t >= 0; --t) {
+    __syncthreads();
+    const int32_t n = t == 0 ? 1 : off[t + 1] - off[t];   // prefixes of length t
+    const double* child = o + off[t + 1];
+    for (int32_t s = tid; s < n; s += kPolicyBlock) {
+      double acc = 0.0;
+      for (int32_t b = 0; b < B; ++b) acc += child[static_cast<int64_t>(s) * B + b];
+      if (t == 0) root = acc;
+      else o[off[t] + s] = acc;
+    }
+  }
+  const double uniform = 1.0 / static_cast<double>(B);
+  for (int32_t t = L; t >= 1; --t) {
+    __syncthreads();
+    const int32_t n = off[t + 1] - off[t];
+    for (int32_t i = tid; i < n; i += kPolicyBlock) {
+      const double pm = t == 1 ? root : o[off[t - 1] + i / B];
+      o[off[t] + i] = pm > 0.0 ? o[off[t] + i] / pm : uniform;
+    }
+  }
+}
+
+// B^L if it is <= limit, else -1 (no overflow: stops at the first product past the limit)
+int64_t pow_limited(int32_t B, int32_t L, int64_t limit) {
+  int64_t n = 1;
+  for (int32_t t = 0; t < L; ++t) {
+    n *= B;
+    if (n > limit) return -1;
+  }
+  return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cs_nash_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ldu,
+                    int64_t ldp_problem, int32_t max_iters, double tol, int variant, double* out_p,
+                    double* out_a, double* out_F, double* out_gap, int32_t* out_iters,
+                    cs_stream_t stream) {
+  const std::string w = "cs_nash_lottery: ";
+  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
+  if (A < 1 || A > kLotMaxA) return fail(CS_ERR_INVALID, w + "need 1 <= A <= 64");
+  if (m < 1 || m > kLotMaxM) return fail(CS_ERR_INVALID, w + "need 1 <= m <= 16384");
+  if (ldu < m) return fail(CS_ERR_INVALID, w + "need ldu >= m");
+  if (ldp_problem < static_cast<int64_t>(A - 1) * ldu + m)
+    return fail(CS_ERR_INVALID, w + "problems overlap (need ldp_problem >= (A - 1) * ldu + m)");
+  if (max_iters < 0) return fail(CS_ERR_INVALID, w + "need max_iters >= 0");
+  if (!std::isfinite(tol)) return fail(CS_ERR_INVALID, w + "tol must be finite");
+  if (variant < 0 || variant > 2) return fail(CS_ERR_INVALID, w + "unknown variant");
+  const size_t u_bytes = static_cast<size_t>(A) * m * sizeof(double);
+  if (variant == 1 && u_bytes > kLotLdsBytes)
+    return fail(CS_ERR_INVALID, w + "variant 1 needs A * m * 8 bytes of LDS, at most 147456");
+  if (P == 0) return CS_OK;
+  if (!U || !out_p) return fail(CS_ERR_INVALID, w + "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(U) % 8 != 0 || reinterpret_cast<uintptr_t>(out_p) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(out_a) % 8 != 0 || reinterpret_cast<uintptr_t>(out_F) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(out_gap) % 8 != 0 || reinterpret_cast<uintptr_t>(out_iters) % 4 != 0)
+    return fail(CS_ERR_INVALID, w + "U and the fp64 outputs must be 8-byte aligned");
+  // variant 0: staged whenever U fits ("The Nash-welfare lottery")
+  const bool staged = variant == 1 || (variant == 0 && u_bytes <= kLotLdsBytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto go = [&](auto block, auto stg) {
+    launch_lottery<decltype(block)::value, decltype(stg)::value>(
+        st, P, decltype(stg)::value ? u_bytes : 0, U, A, m, ldu, ldp_problem, max_iters, tol, out_p,
+        out_a, out_F, out_gap, out_iters);
+  };
+  using std::integral_constant;
+  if (m > kLotWideM) {
+    if (staged) go(integral_constant<int, 1024>{}, std::true_type{});
+    else go(integral_constant<int, 1024>{}, std::false_type{});
+  } else {
+    if (staged) go(integral_constant<int, 256>{}, std::true_type{});
+    else go(integral_constant<int, 256>{}, std::false_type{});
+  }
+  return check_launch("cs_nash_lottery");
+}
+
+int cs_lottery_policy(const double* p, int32_t P, int32_t B, int32_t L, double* out_policy,
+                      cs_stream_t stream) {
+  const std::string w = "cs_lottery_policy: ";
+  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
+  if (B < 1 || L < 1) return fail(CS_ERR_INVALID, w + "need B >= 1 and L >= 1");
+  if (L > kPolicyMaxL) return fail(CS_ERR_INVALID, w + "need L <= 64");
+  const int64_t m = pow_limited(B, L, kLotMaxM);
+  if (m < 0) return fail(CS_ERR_INVALID, w + "need B^L <= 16384");
+  if (P == 0) return CS_OK;
+  if (!p || !out_policy) return fail(CS_ERR_INVALID, w + "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(p) % 8 != 0 || reinterpret_cast<uintptr_t>(out_policy) % 8 != 0)
+    return fail(CS_ERR_INVALID, w + "p and out_policy must be 8-byte aligned");
+  int64_t total = 0, n = 1;
+  for (int32_t t = 1; t <= L; ++t) {
+    n *= B;
+    total += n;
+  }
+  hipLaunchKernelGGL(lottery_policy_kernel, dim3(P), dim3(kPolicyBlock), 0,
+                     static_cast<hipStream_t>(stream), p, B, L, static_cast<int32_t>(m),
+                     static_cast<int32_t>(total), out_policy);
+  return check_launch("cs_lottery_policy");
+}
+
+}  // extern "C"

@@ -1058,3 +1058,65 @@ def rows_from_blocked(vt: torch.Tensor) -> torch.Tensor:
     """Inverse of blocked_vt: [..., nb, D, 32] -> [..., nb * 32, D]."""
     *lead, nb, D, w = vt.shape
     return vt.transpose(-1, -2).reshape(*lead, nb * w, D)
+
+
+def nash_lottery(U: torch.Tensor, max_iters: int = 1000, tol: float = 1e-10,
+                 variant: int = 0) -> Dict[str, torch.Tensor]:
+    """The Nash-welfare lottery of every problem of U in one launch (cs_nash_lottery).
+
+    U [A, m] or [P, A, m] float64 utilities with unit column stride (A <= 64, m <= 16384).
+    Returns {"p": [.., m] the lottery, "a": [.., A] = U p, "F": [..] = sum_i log a_i,
+    "gap": [..] the Frank-Wolfe certificate max_j g_j - A, "iters": [..] int32}; a problem with
+    a negative or non-finite utility or an all-zero agent row gets iters = -1 and NaN.
+    variant: 0 the library's choice, 1 U staged in LDS, 2 U read from global memory (bitwise
+    equal outputs).  Restates FW_nash_welfare (core.py:116-168)."""
+    L = _lib.load()
+    if U.dim() not in (2, 3) or U.dtype != torch.float64 or (U.stride(-1) != 1 and U.shape[-1] > 1):
+        raise CSError("U must be [A, m] or [P, A, m] float64 with unit column stride")
+    _require_cuda(U)
+    batched = U.dim() == 3
+    P = U.shape[0] if batched else 1
+    A, m = U.shape[-2], U.shape[-1]
+    ldu = U.stride(-2) if A > 1 else m
+    ldp = U.stride(0) if batched and P > 1 else max(A, 1) * ldu
+    dev = U.device
+    p = torch.empty((P, m), dtype=torch.float64, device=dev)
+    a = torch.empty((P, A), dtype=torch.float64, device=dev)
+    F = torch.empty(P, dtype=torch.float64, device=dev)
+    gap = torch.empty(P, dtype=torch.float64, device=dev)
+    iters = torch.empty(P, dtype=torch.int32, device=dev)
+    rc = L.cs_nash_lottery(U.data_ptr(), P, A, m, ldu, ldp, int(max_iters), float(tol), int(variant),
+                           p.data_ptr(), a.data_ptr(), F.data_ptr(), gap.data_ptr(),
+                           iters.data_ptr(), _stream())
+    _lib.check(rc, "cs_nash_lottery")
+    out = {"p": p, "a": a, "F": F, "gap": gap, "iters": iters}
+    return out if batched else {k: v[0] for k, v in out.items()}
+
+
+def lottery_policy(p: torch.Tensor, B: int, L: int):
+    """The token policy a lottery over the B^L leaves (lexicographic order) induces
+    (cs_lottery_policy): a list over the levels t = 0..L-1 of pi[t][s, b] = mass(s + b) / mass(s),
+    [B^t, B] float64 (with a leading P for p [P, m]), views of one output; a prefix of mass <= 0
+    has the uniform 1/B.  Restates the masses and step probabilities of induced_policy_rollout
+    (core.py:303-325)."""
+    L_ = _lib.load()
+    B, L = int(B), int(L)
+    if p.dim() not in (1, 2) or p.dtype != torch.float64 or not p.is_contiguous():
+        raise CSError("p must be a contiguous float64 [m] or [P, m] tensor")
+    _require_cuda(p)
+    batched = p.dim() == 2
+    P = p.shape[0] if batched else 1
+    sizes = [B ** (t + 1) for t in range(L)] if 1 <= B and 1 <= L <= 64 else [0]
+    if sizes[-1] > 16384:
+        sizes = [0]          # the entry point rejects the shape; nothing that large is allocated
+    if sizes[-1] and p.shape[-1] != sizes[-1]:
+        raise CSError(f"p has {p.shape[-1]} leaves, B^L is {sizes[-1]}")
+    out = torch.empty((P, sum(sizes)), dtype=torch.float64, device=p.device)
+    rc = L_.cs_lottery_policy(p.data_ptr(), P, B, L, out.data_ptr(), _stream())
+    _lib.check(rc, "cs_lottery_policy")
+    levels, at = [], 0
+    for n in sizes:
+        blk = out[:, at:at + n].view(P, n // B, B)
+        levels.append(blk if batched else blk[0])
+        at += n
+    return levels

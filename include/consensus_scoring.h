@@ -511,6 +511,53 @@ int cs_gemm_bf16_packed(const void* x, int64_t ldx, const void* w_packed, void* 
                         int64_t M, int64_t N, int64_t K, int splits, int gated, int act,
                         int variant, float* workspace, cs_stream_t stream);
 
+/*
+ * cs_nash_lottery — the lottery over m complete statements that maximises Nash welfare
+ * F(p) = sum_i log(U_i . p), for P independent problems in one launch, one workgroup each:
+ * Frank-Wolfe towards the vertex e_j* of largest gradient g_j = sum_i U[i,j] / a_i (a = U p,
+ * agents in index order, lowest j on ties) with a golden-section search of the step gamma in
+ * [0, 1] (at most 80 rounds, until the bracket is under 1e-9, gamma* its midpoint), from
+ * p = 1/m.  An iteration adopts p <- (1 - gamma*) p + gamma* e_j* and then stops when F grew by
+ * less than tol; max_iters = 0 returns the uniform lottery.  All fp64 (utilities reach down to
+ * 1e-300); a is carried as a <- (1 - gamma*) a + gamma* U[:,j*] between iterations.
+ *
+ * U: P problems of [A][ldu] fp64 (first m columns used), problem stride ldp_problem (elements;
+ * problems must not overlap), 8-byte aligned.  1 <= A <= 64, 1 <= m <= 16384, ldu >= m,
+ * P >= 0, max_iters >= 0, tol finite.
+ * variant: 0 = the library's choice, 1 = the problem's U is staged in LDS once (invalid when
+ * A * m * 8 exceeds the 147456 bytes the kernel may take), 2 = U is read from global memory
+ * every iteration.  Same arithmetic in the same order: the variants' outputs are bitwise equal.
+ *
+ * out_p [P][m] the lottery; nullable: out_a [P][A] = U p, out_F [P] = sum_i log a_i,
+ * out_gap [P] = max_j g_j - A (the Frank-Wolfe certificate: F* - F(p) <= gap by concavity),
+ * all three recomputed from the p written; out_iters [P] the iterations run.
+ * A problem that holds a negative or non-finite utility, or an agent whose row is all zero,
+ * gets out_iters = -1 and NaN in its other outputs; the rest of the batch is unaffected.
+ * Deterministic (no atomics), no host sync, no allocation.
+ *
+ * Replaces: FW_nash_welfare (core.py:116-168) and F_val at its result (core.py:108-113), called
+ *   once per (seed, rho) by the reference's sweep (core.py:365-369).
+ */
+int cs_nash_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ldu,
+                    int64_t ldp_problem, int32_t max_iters, double tol, int variant, double* out_p,
+                    double* out_a, double* out_F, double* out_gap, int32_t* out_iters,
+                    cs_stream_t stream);
+
+/*
+ * cs_lottery_policy — the token-level policy a lottery over the m = B^L leaves of a B-ary tree
+ * of depth L induces: pi(b | s) = mass(s + b) / mass(s), where mass(s) is the lottery's weight
+ * on the contiguous block of leaves under prefix s (leaves in lexicographic order); a prefix of
+ * mass <= 0 gets the uniform 1/B.  Masses are summed bottom-up in action order, fp64.
+ * p [P][m] contiguous; out_policy [P][sum_{t=1..L} B^t]: per problem the levels t = 0..L-1
+ * concatenated, level t holding [B^t prefixes][B actions].  One workgroup per problem.
+ * B >= 1, L >= 1, B^L <= 16384 (and L <= 64, which only binds at B = 1).
+ *
+ * Replaces: the prefix masses and per-step action probabilities of induced_policy_rollout
+ *   (core.py:303-325, over build_prefix_index's table, core.py:287-294).
+ */
+int cs_lottery_policy(const double* p, int32_t P, int32_t B, int32_t L, double* out_policy,
+                      cs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
