@@ -3,7 +3,9 @@ the engine paths built on them, against plain PyTorch fp32 references of the sam
 
 cs_prefix_attention is bf16 in / bf16 out with fp32 softmax and a bf16 P for the P.V
 MFMA, so it is held to bf16 tolerance against an fp32 attention over the SAME bf16
-inputs (|err| <= 2e-2 + 2e-2 |ref|; measured errors are ~4e-3).  The engine-level tests
+inputs (|err| <= 2e-2 + 2e-2 |ref|; measured errors are ~4e-3); its mask edges, softmax
+rescale, wave combine and split merge are pinned by planted-key and staircase inputs in
+tests/test_attention_edges_gpu.py.  The engine-level tests
 compare the fused decode (forward_streams / DecodeState) with the eager SDPA path of the
 same bf16 model: token log-probs within 3e-2 (both paths round activations to bf16 at
 different points), and graph replay against eager execution of the fused path bit for
