@@ -4,7 +4,11 @@ reference, SURVEY.md §8(d) "parity gates"), the gated gate|up form against cs_g
 the rounded GEMM halves, K splits against no split, and bitwise run-to-run determinism.
 
 Tolerance: |y - ref| <= 2^-7 |ref| + 1e-3 * max|ref| — one bf16 rounding of the output
-(relative 2^-8) plus fp32 accumulation-order differences over K <= 14336."""
+(relative 2^-8) plus fp32 accumulation-order differences over K <= 14336.
+
+That tolerance cannot see the output rounding mode or one dropped K chunk at long K:
+tests/test_gemm_exact_gpu.py holds every template instantiation to zero tolerance on
+integer operands (expectations from the host, tests/gemm_ref.py)."""
 import pytest
 import torch
 
