@@ -11,6 +11,15 @@
 //                        stream's own tokens (history + causal self) live in a per-stream
 //                        buffer and are attended in the same pass.  bf16 MFMA
 //                        (v_mfma_f32_16x16x32_bf16), fp32 online softmax.
+//                        Two kernels, built from one set of pieces (each written once, below):
+//                        tile_rows / hist_blocks (who a lane is, which history blocks its rows
+//                        see), block_mask / prefix_block / hist_block (where a key block lives
+//                        and what of it a row may see), load_q, attend_block (the arithmetic),
+//                        fetch_chunks / stage_chunks / attend_staged under CS_ATTEND_STAGED
+//                        (key blocks staged through LDS, double-buffered), combine_waves,
+//                        store_out.  prefix_attn_lds_kernel stages every block of the
+//                        workgroup's list; prefix_attn_plan_lds_kernel stages its split's
+//                        prefix blocks and loads its tiles' history per wave.
 //   attn_merge_kernel    fixed-order merge of the key splits (no float atomics).
 //   rope_place_kernel    RoPE on the fused q|k|v projection + placement of the new K (row
 //                        layout) and V (transposed layout) into the per-stream buffers;
@@ -111,57 +120,161 @@ struct KeyBlock {
   bf16x4 vlo[D / 16], vhi[D / 16];
 };
 
-// where key block `it` of a query tile lives: the prefix blocks first, then the history
-// blocks of the tile's streams b_lo .. (nbh blocks each)
-struct ItemRef {
-  const __bf16* k;   // this lane's first K row
-  const __bf16* v;   // this lane's first V^T row
-  int kb, lim, pos0;
+// This lane's place in a workgroup: the workgroup holds query rows r0 .. r0 + nrows - 1 of
+// (group gi, K/V head g) -- row = ((stream b) * T + token t) * rep + head of the K/V head --
+// as n_qt tiles of 16; wave w attends tile qt's key blocks ks, ks + kw, ... (kw waves share a
+// tile when the workgroup has fewer than four), lane (col, h4) query column col of the tile.
+struct TileRows {
+  int gi, g;             // group, K/V head
+  int M, r0, nrows;      // the (group, head)'s query rows; the workgroup's first row and count
+  int n_qt, kw;          // 16-row tiles; waves per tile
+  int w, lane, qt, ks;   // wave, lane, the wave's tile and key-block stripe
+  bool active;           // ks < kw: the wave has a tile
+  int col, h4;           // lane & 15, lane >> 4
+  bool vrow;             // active and the lane's row exists
+  int t, b;              // the row's token and stream (the last row's when !vrow)
+  int64_t tok;           // its q / out token index
+  int head;
+  int hb, pl;            // *hist_base; the group's prefix length
+  int64_t po;            // ... and its first key row in k_pfx / vt_pfx
+  int hv;                // history keys the row sees: slots [0, hv)
+  int kmin_pos;          // first position inside the row's window (INT32_MIN: no window)
 };
 
-__device__ __forceinline__ ItemRef item_ref(const AttnParams& a, int it, int nbp, int nbh, int b_lo,
-                                            int b, int gi, int g, int64_t po, int pl, int hv,
-                                            bool vrow, int col, int h4, int D) {
-  ItemRef r;
-  if (it < nbp) {
-    r.kb = it * kKeyBlock;
-    const int64_t k0 = static_cast<int64_t>(g) * a.ldp + po;
-    r.k = a.kp + (k0 + r.kb + col) * D + 8 * h4;
-    r.v = a.vtp + (k0 + r.kb) * D + col * kKeyBlock + 4 * h4;
-    r.lim = vrow ? pl : 0;
-    r.pos0 = 0;
-  } else {
-    const int ih = it - nbp;
-    const int bb = b_lo + ih / nbh;
-    r.kb = (ih % nbh) * kKeyBlock;
-    const int64_t sh = (static_cast<int64_t>(gi) * a.n_str + bb) * a.Hkv + g;
-    r.k = a.kh + (sh * a.ldh + r.kb + col) * D + 8 * h4;
-    r.v = a.vth + (sh * a.ldh + r.kb) * D + col * kKeyBlock + 4 * h4;
-    r.lim = (vrow && bb == b) ? hv : 0;
-    r.pos0 = pl;
-  }
+// pg = group * Hkv + K/V head, qg = which 64 rows of it
+__device__ __forceinline__ TileRows tile_rows(const AttnParams& a, int pg, int qg) {
+  TileRows r;
+  r.gi = pg / a.Hkv;
+  r.g = pg % a.Hkv;
+  const int p = a.gpfx ? a.gpfx[r.gi] : r.gi;
+  r.M = a.n_str * a.T * a.rep;
+  r.r0 = qg * kGroupRows;
+  r.nrows = min(kGroupRows, r.M - r.r0);
+  r.n_qt = (r.nrows + 15) >> 4;
+  r.kw = r.n_qt == 1 ? 4 : (r.n_qt == 2 ? 2 : 1);
+  const int tid = threadIdx.x;
+  r.w = tid >> 6;
+  r.lane = tid & 63;
+  r.qt = r.w % r.n_qt;
+  r.ks = r.w / r.n_qt;
+  r.active = r.ks < r.kw;
+  r.col = r.lane & 15;
+  r.h4 = r.lane >> 4;
+
+  const int row = r.r0 + r.qt * 16 + r.col;
+  r.vrow = r.active && row < r.M;
+  const int rr = row < r.M ? row : r.M - 1;
+  const int jh = rr % a.rep, bt = rr / a.rep;
+  r.t = bt % a.T;
+  r.b = bt / a.T;
+  r.tok = (static_cast<int64_t>(r.gi) * a.n_str + r.b) * a.T + r.t;
+  r.head = r.g * a.rep + jh;
+  r.hb = *a.hist_base;
+  r.pl = a.plen[p];
+  r.po = a.poff[p];
+  r.hv = min(r.hb + r.t + 1, static_cast<int>(a.ldh));
+  r.kmin_pos = a.window > 0 ? r.pl + r.hb + r.t - a.window + 1 : INT32_MIN;
   return r;
 }
 
-// all of a block's loads issued back to back (one memory round trip per block)
+// The history key blocks that rows row0 .. row1 of a (group, head) can see (uniform over
+// whoever shares the rows: the workgroup's 64, a wave's 16): nbh blocks -- up to the furthest
+// query's causal limit hlim -- of each stream the rows touch, b_lo on; n blocks in all.
+struct HistBlocks {
+  int b_lo, nbh, n, hlim;
+};
+
+__device__ __forceinline__ HistBlocks hist_blocks(const AttnParams& a, int hb, int row0, int row1) {
+  HistBlocks h;
+  h.b_lo = (row0 / a.rep) / a.T;
+  const int b_hi = (row1 / a.rep) / a.T;
+  const int t_hi = h.b_lo == b_hi ? (row1 / a.rep) % a.T : a.T - 1;
+  h.hlim = min(hb + t_hi + 1, static_cast<int>(a.ldh));
+  h.nbh = (h.hlim + kKeyBlock - 1) / kKeyBlock;
+  h.n = (b_hi - h.b_lo + 1) * h.nbh;
+  return h;
+}
+
+// what attend_block masks a block's keys by: key kb + j is visible iff kb + j < lim and its
+// position pos0 + kb + j >= the row's kmin_pos
+struct BlockMask {
+  int kb, lim, pos0;
+};
+
+// the lane's mask of key block kb of the prefix, or (hist) of stream bb's history: a row that
+// does not exist sees nothing, a row of another stream nothing of bb's
+__device__ __forceinline__ BlockMask block_mask(const TileRows& tr, int kb, bool hist, int bb) {
+  BlockMask k;
+  k.kb = kb;
+  k.lim = hist ? ((tr.vrow && bb == tr.b) ? tr.hv : 0) : (tr.vrow ? tr.pl : 0);
+  k.pos0 = hist ? tr.pl : 0;
+  return k;
+}
+
+// The K rows and V^T tiles of the prefixes and of the history, read from the kernel arguments
+// once per kernel: a block list that picks prefix or history per block would otherwise load
+// the pointers it picks between inside its loop (a scalar load and a wait per staged block).
+struct KvBase {
+  const __bf16 *kp, *vtp, *kh, *vth;
+};
+__device__ __forceinline__ KvBase kv_base(const AttnParams& a) { return {a.kp, a.vtp, a.kh, a.vth}; }
+
+// where a key block lives (its 32 K rows and its V^T tile, each contiguous) and its mask
+struct BlockRef {
+  const __bf16* k;
+  const __bf16* vt;
+  BlockMask mask;
+};
+
+// block blk of the group's prefix
 template <int D>
-__device__ __forceinline__ void load_block(KeyBlock<D>& f, const ItemRef& r) {
+__device__ __forceinline__ BlockRef prefix_block(const AttnParams& a, const KvBase& kv, const TileRows& tr,
+                                                int blk) {
+  BlockRef r;
+  r.mask = block_mask(tr, blk * kKeyBlock, false, 0);
+  const int64_t k0 = static_cast<int64_t>(tr.g) * a.ldp + tr.po + r.mask.kb;
+  r.k = kv.kp + k0 * D;
+  r.vt = kv.vtp + k0 * D;
+  return r;
+}
+
+// history block ih of h's list: block ih % nbh of stream b_lo + ih / nbh (V^T-tile layout;
+// the row layout takes the mask alone)
+template <int D>
+__device__ __forceinline__ BlockRef hist_block(const AttnParams& a, const KvBase& kv, const TileRows& tr,
+                                               const HistBlocks& h, int ih) {
+  BlockRef r;
+  const int bb = h.b_lo + ih / h.nbh;
+  r.mask = block_mask(tr, (ih % h.nbh) * kKeyBlock, true, bb);
+  const int64_t sh = (static_cast<int64_t>(tr.gi) * a.n_str + bb) * a.Hkv + tr.g;
+  const int64_t k0 = sh * a.ldh + r.mask.kb;
+  r.k = kv.kh + k0 * D;
+  r.vt = kv.vth + k0 * D;
+  return r;
+}
+
+// a block straight from global memory (the plan kernel's per-wave V^T-tile history): all of
+// its loads issued back to back (one memory round trip per block)
+template <int D>
+__device__ __forceinline__ void load_block(KeyBlock<D>& f, const BlockRef& r, int col, int h4) {
+  const __bf16* k = r.k + col * D + 8 * h4;
+  const __bf16* v = r.vt + col * kKeyBlock + 4 * h4;
 #pragma unroll
   for (int ds = 0; ds < D / 32; ++ds) {
-    f.k0[ds] = *reinterpret_cast<const bf16x8*>(r.k + ds * 32);
-    f.k1[ds] = *reinterpret_cast<const bf16x8*>(r.k + 16 * D + ds * 32);
+    f.k0[ds] = *reinterpret_cast<const bf16x8*>(k + ds * 32);
+    f.k1[ds] = *reinterpret_cast<const bf16x8*>(k + 16 * D + ds * 32);
   }
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) {
-    f.vlo[dt] = *reinterpret_cast<const bf16x4*>(r.v + dt * 16 * kKeyBlock);
-    f.vhi[dt] = *reinterpret_cast<const bf16x4*>(r.v + dt * 16 * kKeyBlock + 16);
+    f.vlo[dt] = *reinterpret_cast<const bf16x4*>(v + dt * 16 * kKeyBlock);
+    f.vhi[dt] = *reinterpret_cast<const bf16x4*>(v + dt * 16 * kKeyBlock + 16);
   }
 }
 
 // S^T = K . Q^T for the block's 32 keys, online softmax update, O^T += V^T . P^T
 template <int D>
 __device__ __forceinline__ void attend_block(const AttnParams& a, const KeyBlock<D>& f,
-                                             const ItemRef& r, const bf16x8 (&qf)[D / 32],
+                                             const BlockMask& r, const bf16x8 (&qf)[D / 32],
                                              int kmin_pos, int h4, f32x4 (&o)[D / 16], float& m,
                                              float& l) {
   f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
@@ -242,15 +355,25 @@ __device__ __forceinline__ void attend_block(const AttnParams& a, const KeyBlock
   }
 }
 
-// Scoring chunks and prompt prefill (no plan, T > 1, >= 1024 cells): the workgroup's four
-// 16-row query tiles walk ONE key-block list — the agent's prefix blocks, then the history
-// blocks of every stream the 64 rows touch, up to the furthest query's causal limit — and
-// each 32-key block is staged through LDS once per workgroup (K rows padded to D + 8, V^T
-// rows to 40 keys: conflict-free fragment reads), double-buffered: the next block's 16-byte
-// global loads are in flight while the current one is attended from LDS (loading every
-// block once per tile instead is 4x the L2 traffic for 64 rows of one stream).  Blocks
-// outside a tile's own stream or causal range are masked per lane; the arithmetic of a
-// block is attend_block's.
+// the lane's Q fragments (its row's 8 d of each 32-wide d step); zeros for a row that does
+// not exist
+template <int D>
+__device__ __forceinline__ void load_q(const AttnParams& a, const TileRows& tr, bf16x8 (&qf)[D / 32]) {
+  const __bf16* qrow = a.q + (tr.tok * a.H + tr.head) * D + 8 * tr.h4;
+#pragma unroll
+  for (int ds = 0; ds < D / 32; ++ds) {
+    if (tr.vrow) {
+      qf[ds] = *reinterpret_cast<const bf16x8*>(qrow + ds * 32);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) qf[ds][e] = static_cast<__bf16>(0.0f);
+    }
+  }
+}
+
+// A key block staged through LDS once per workgroup: K rows padded to D + 8, V^T rows to 40
+// keys (conflict-free fragment reads), two buffers.  The same LDS holds the wave combine
+// (combine_waves: three waves' O, m, l of 16 rows) once the key blocks are done.
 template <int D>
 struct LdsTile {
   static constexpr int KROW = D + 8;                 // bf16 per staged K row
@@ -259,168 +382,113 @@ struct LdsTile {
   static constexpr int VELEMS = D * VROW;
   static constexpr int ELEMS = KELEMS + VELEMS;      // one buffer
   static constexpr int NCH = D / 64;                 // 16-byte chunks per thread per operand
+  static constexpr int LDSW = D + 2;                 // floats per combined row: O, m, l
+  static constexpr int kBufBytes = 2 * ELEMS * 2;
+  static constexpr int kCombBytes = 3 * 16 * LDSW * 4;
+  static constexpr int kBytes = kBufBytes > kCombBytes ? kBufBytes : kCombBytes;
 };
 
-// D = 256: one wave per SIMD (two: 208 B/lane of spills)
+// staging: thread tid copies 16-byte chunks c = tid + 256 j of the block's K (row c / (D/8))
+// and V^T (d row c / 4, keys 8 (c % 4) ..): global -> registers ...
 template <int D>
-__global__ __launch_bounds__(kAttnThreads, D <= 128 ? 2 : 1)
-void prefix_attn_lds_kernel(AttnParams a) {
+__device__ __forceinline__ void fetch_chunks(const BlockRef& r, u32x4 (&rk)[LdsTile<D>::NCH],
+                                             u32x4 (&rv)[LdsTile<D>::NCH]) {
+#pragma unroll
+  for (int j = 0; j < LdsTile<D>::NCH; ++j) {
+    const int c = static_cast<int>(threadIdx.x) + kAttnThreads * j;
+    rk[j] = *reinterpret_cast<const u32x4*>(r.k + c * 8);
+    rv[j] = *reinterpret_cast<const u32x4*>(r.vt + c * 8);
+  }
+}
+
+// ... registers -> block j's padded buffer, j & 1.  256 is a whole number of K and of V^T
+// rows, so chunk c's place is chunk tid's plus a compile-time offset: one address per operand
+template <int D>
+__device__ __forceinline__ void stage_chunks(__bf16* buf, int j, const u32x4 (&rk)[LdsTile<D>::NCH],
+                                             const u32x4 (&rv)[LdsTile<D>::NCH]) {
   using LT = LdsTile<D>;
-  constexpr int NDS = D / 32;
-  constexpr int NDT = D / 16;
-  constexpr int LDSW = D + 2;
-  constexpr int kBufBytes = 2 * LT::ELEMS * 2;
-  constexpr int kCombBytes = 3 * 16 * LDSW * 4;
-  __shared__ __attribute__((aligned(16))) char lds[kBufBytes > kCombBytes ? kBufBytes : kCombBytes];
-  __bf16* buf = reinterpret_cast<__bf16*>(lds);
-  auto sm = reinterpret_cast<float (*)[16][LDSW]>(lds);   // the wave combine, after the loop
-
-  const int bid = logical_block(a.swizzle);
-  const int qg = bid % a.n_qg, pg = bid / a.n_qg;
-  const int gi = pg / a.Hkv, g = pg % a.Hkv;
-  const int p = a.gpfx ? a.gpfx[gi] : gi;
-  const int M = a.n_str * a.T * a.rep;
-  const int r0 = qg * kGroupRows;
-  const int nrows = min(kGroupRows, M - r0);
-  const int n_qt = (nrows + 15) >> 4;
-  const int kw = n_qt == 1 ? 4 : (n_qt == 2 ? 2 : 1);
+  __bf16* kd = buf + (j & 1) * LT::ELEMS;
+  __bf16* vd = kd + LT::KELEMS;
   const int tid = threadIdx.x;
-  const int w = tid >> 6, lane = tid & 63;
-  const int qt = w % n_qt, ks = w / n_qt;
-  const bool active = ks < kw;
-  const int col = lane & 15, h4 = lane >> 4;
-
-  const int row = r0 + qt * 16 + col;
-  const bool vrow = active && row < M;
-  const int rr = row < M ? row : M - 1;
-  const int jh = rr % a.rep, bt = rr / a.rep;
-  const int t = bt % a.T, b = bt / a.T;
-  const int64_t tok = (static_cast<int64_t>(gi) * a.n_str + b) * a.T + t;
-  const int head = g * a.rep + jh;
-  const int hb = *a.hist_base;
-  const int pl = a.plen[p];
-  const int64_t po = a.poff[p];
-  const int hv = min(hb + t + 1, static_cast<int>(a.ldh));
-  const int kmin_pos = a.window > 0 ? pl + hb + t - a.window + 1 : INT32_MIN;
-
-  // the workgroup's key blocks (uniform): prefix, then nbh history blocks per stream b_lo..b_hi
-  const int rw1 = r0 + nrows - 1;
-  const int b_lo = (r0 / a.rep) / a.T, b_hi = (rw1 / a.rep) / a.T;
-  const int t_hi = b_lo == b_hi ? (rw1 / a.rep) % a.T : a.T - 1;
-  const int nbh = (min(hb + t_hi + 1, static_cast<int>(a.ldh)) + kKeyBlock - 1) / kKeyBlock;
-  const int nbp = (pl + kKeyBlock - 1) / kKeyBlock;
-  const int n_items = nbp + (b_hi - b_lo + 1) * nbh;
-
-  // item it: global K rows / V^T tile of 32 keys (contiguous) and this lane's mask data
-  auto item_src = [&](int it, const __bf16*& ks_, const __bf16*& vs_) {
-    if (it < nbp) {
-      const int64_t k0 = static_cast<int64_t>(g) * a.ldp + po + it * kKeyBlock;
-      ks_ = a.kp + k0 * D;
-      vs_ = a.vtp + k0 * D;
-    } else {
-      const int ih = it - nbp;
-      const int bb = b_lo + ih / nbh;
-      const int64_t sh = (static_cast<int64_t>(gi) * a.n_str + bb) * a.Hkv + g;
-      const int64_t k0 = sh * a.ldh + (ih % nbh) * kKeyBlock;
-      ks_ = a.kh + k0 * D;
-      vs_ = a.vth + k0 * D;
-    }
-  };
-  auto item_mask = [&](int it) {
-    ItemRef r;
-    r.k = nullptr;
-    r.v = nullptr;
-    if (it < nbp) {
-      r.kb = it * kKeyBlock;
-      r.lim = vrow ? pl : 0;
-      r.pos0 = 0;
-    } else {
-      const int ih = it - nbp;
-      const int bb = b_lo + ih / nbh;
-      r.kb = (ih % nbh) * kKeyBlock;
-      r.lim = (vrow && bb == b) ? hv : 0;
-      r.pos0 = pl;
-    }
-    return r;
-  };
-  // staging: thread tid copies 16-byte chunks c = tid + 256 j of K (row c / (D/8)) and of
-  // V^T (d row c / 4, keys 8 (c % 4) ..)
-  u32x4 rk[LT::NCH], rv[LT::NCH];
-  auto fetch = [&](int it) {
-    const __bf16 *ksrc, *vsrc;
-    item_src(it, ksrc, vsrc);
+  __bf16* kt = kd + (tid / (D / 8)) * LT::KROW + (tid % (D / 8)) * 8;
+  __bf16* vt = vd + (tid >> 2) * LT::VROW + (tid & 3) * 8;
 #pragma unroll
-    for (int j = 0; j < LT::NCH; ++j) {
-      const int c = tid + kAttnThreads * j;
-      rk[j] = *reinterpret_cast<const u32x4*>(ksrc + c * 8);
-      rv[j] = *reinterpret_cast<const u32x4*>(vsrc + c * 8);
-    }
-  };
-  auto stage = [&](int sbuf) {
-    __bf16* kd = buf + sbuf * LT::ELEMS;
-    __bf16* vd = kd + LT::KELEMS;
-#pragma unroll
-    for (int j = 0; j < LT::NCH; ++j) {
-      const int c = tid + kAttnThreads * j;
-      *reinterpret_cast<u32x4*>(kd + (c / (D / 8)) * LT::KROW + (c % (D / 8)) * 8) = rk[j];
-      *reinterpret_cast<u32x4*>(vd + (c >> 2) * LT::VROW + (c & 3) * 8) = rv[j];
-    }
-  };
-
-  bf16x8 qf[NDS];
-  {
-    const __bf16* qrow = a.q + (tok * a.H + head) * D + 8 * h4;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) {
-      if (vrow) {
-        qf[ds] = *reinterpret_cast<const bf16x8*>(qrow + ds * 32);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qf[ds][e] = static_cast<__bf16>(0.0f);
-      }
-    }
+  for (int i = 0; i < LT::NCH; ++i) {
+    *reinterpret_cast<u32x4*>(kt + i * (kAttnThreads / (D / 8)) * LT::KROW) = rk[i];
+    *reinterpret_cast<u32x4*>(vt + i * (kAttnThreads / 4) * LT::VROW) = rv[i];
   }
-  f32x4 o[NDT];
-#pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m = -INFINITY, l = 0.0f;
+}
 
-  if (n_items > 0) {
-    fetch(0);
-    stage(0);
-  }
-  __syncthreads();
-  for (int it = 0; it < n_items; ++it) {
-    const bool more = it + 1 < n_items;
-    if (more) fetch(it + 1);
-    if (active && (it % kw) == ks) {
-      const __bf16* kd = buf + (it & 1) * LT::ELEMS;
-      const __bf16* vd = kd + LT::KELEMS;
-      KeyBlock<D> f;
+// the staged block j (buffer j & 1) attended by this wave; mine_staged: is it this wave's --
+// the tile's wave ks takes the blocks j % kw == ks
+__device__ __forceinline__ bool mine_staged(const TileRows& tr, int j) {
+  return tr.active && (j % tr.kw) == tr.ks;
+}
+
+template <int D, typename Ref>
+__device__ __forceinline__ void attend_staged(const AttnParams& a, const TileRows& tr, const __bf16* buf,
+                                              int j, Ref ref, const bf16x8 (&qf)[D / 32],
+                                              f32x4 (&o)[D / 16], float& m, float& l) {
+  using LT = LdsTile<D>;
+  const int col = tr.col, h4 = tr.h4;
+  const __bf16* kd = buf + (j & 1) * LT::ELEMS;
+  const __bf16* vd = kd + LT::KELEMS;
+  KeyBlock<D> f;
 #pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) {
-        f.k0[ds] = *reinterpret_cast<const bf16x8*>(kd + col * LT::KROW + ds * 32 + 8 * h4);
-        f.k1[ds] = *reinterpret_cast<const bf16x8*>(kd + (16 + col) * LT::KROW + ds * 32 + 8 * h4);
-      }
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        f.vlo[dt] = *reinterpret_cast<const bf16x4*>(vd + (dt * 16 + col) * LT::VROW + 4 * h4);
-        f.vhi[dt] = *reinterpret_cast<const bf16x4*>(vd + (dt * 16 + col) * LT::VROW + 16 + 4 * h4);
-      }
-      attend_block<D>(a, f, item_mask(it), qf, kmin_pos, h4, o, m, l);
-    }
-    if (more) stage((it + 1) & 1);   // buffer (it + 1) & 1 was last read in iteration it - 1
-    __syncthreads();
+  for (int ds = 0; ds < D / 32; ++ds) {
+    f.k0[ds] = *reinterpret_cast<const bf16x8*>(kd + col * LT::KROW + ds * 32 + 8 * h4);
+    f.k1[ds] = *reinterpret_cast<const bf16x8*>(kd + (16 + col) * LT::KROW + ds * 32 + 8 * h4);
   }
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) {
+    f.vlo[dt] = *reinterpret_cast<const bf16x4*>(vd + (dt * 16 + col) * LT::VROW + 4 * h4);
+    f.vhi[dt] = *reinterpret_cast<const bf16x4*>(vd + (dt * 16 + col) * LT::VROW + 16 + 4 * h4);
+  }
+  attend_block<D>(a, f, ref(j).mask, qf, tr.kmin_pos, h4, o, m, l);
+}
+
+// The staged pipeline: the workgroup's key blocks ref(0) .. ref(n - 1) (n uniform; ref(j): a
+// BlockRef), each staged once and attended by every tile, double-buffered -- block j + 1's
+// 16-byte global loads are in flight while block j is attended from LDS, staged after it
+// (buffer (j + 1) & 1 was last read in iteration j - 1), one barrier per block.
+// Expanded in the kernel body, not called: with this loop in a function of its own, however
+// it is passed its operands, prefix_attn_plan_lds_kernel<128, true> needs 170-172 VGPRs for
+// the same instructions (168, three waves per SIMD, when it is expanded in place).
+#define CS_ATTEND_STAGED(D, a, tr, lds, n_blocks, ref, qf, o, m, l)                         \
+  do {                                                                                      \
+    using LT_ = LdsTile<D>;                                                                 \
+    const int n_ = (n_blocks);                                                              \
+    __bf16* buf_ = reinterpret_cast<__bf16*>(lds);                                          \
+    u32x4 rk_[LT_::NCH], rv_[LT_::NCH];                                                     \
+    if (n_ > 0) {                                                                           \
+      fetch_chunks<D>(ref(0), rk_, rv_);                                                    \
+      stage_chunks<D>(buf_, 0, rk_, rv_);                                                   \
+    }                                                                                       \
+    __syncthreads();                                                                        \
+    for (int j_ = 0; j_ < n_; ++j_) {                                                       \
+      const bool more_ = j_ + 1 < n_;                                                       \
+      if (more_) fetch_chunks<D>(ref(j_ + 1), rk_, rv_);                                    \
+      if (mine_staged(tr, j_)) attend_staged<D>(a, tr, buf_, j_, ref, qf, o, m, l);   \
+      if (more_) stage_chunks<D>(buf_, j_ + 1, rk_, rv_);                                   \
+      __syncthreads();                                                                      \
+    }                                                                                       \
+  } while (0)
+
+// l summed over the lane groups, then the waves that share a query tile combine through LDS
+// into the tile's wave ks = 0 (fixed order: ks = 0, 1, ...).  Every wave of the workgroup
+// calls this, after a barrier that ends the last use of the LDS.
+template <int D>
+__device__ __forceinline__ void combine_waves(const TileRows& tr, char* lds, f32x4 (&o)[D / 16],
+                                              float& m, float& l) {
+  auto sm = reinterpret_cast<float (*)[16][LdsTile<D>::LDSW]>(lds);
+  const int n_qt = tr.n_qt, kw = tr.kw, col = tr.col, h4 = tr.h4;
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
-
-  // waves that share a query tile combine through LDS (fixed order: ks = 0, 1, ...)
   if (kw > 1) {
-    if (active && ks > 0) {
-      const int sl = w - n_qt;
+    if (tr.active && tr.ks > 0) {
+      const int sl = tr.w - n_qt;
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt)
+      for (int dt = 0; dt < D / 16; ++dt)
 #pragma unroll
         for (int i = 0; i < 4; ++i) sm[sl][col][dt * 16 + 4 * h4 + i] = o[dt][i];
       if (h4 == 0) {
@@ -429,36 +497,74 @@ void prefix_attn_lds_kernel(AttnParams a) {
       }
     }
     __syncthreads();
-    if (active && ks == 0) {
+    if (tr.active && tr.ks == 0) {
       float mt = m;
-      for (int k = 1; k < kw; ++k) mt = fmaxf(mt, sm[qt + n_qt * k - n_qt][col][D]);
+      for (int k = 1; k < kw; ++k) mt = fmaxf(mt, sm[tr.qt + n_qt * k - n_qt][col][D]);
       const float c0 = mt == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(m - mt);
       l *= c0;
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) o[dt] *= c0;
+      for (int dt = 0; dt < D / 16; ++dt) o[dt] *= c0;
       for (int k = 1; k < kw; ++k) {
-        const int sl = qt + n_qt * k - n_qt;
+        const int sl = tr.qt + n_qt * k - n_qt;
         const float mk = sm[sl][col][D];
         const float ck = mt == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mk - mt);
         l = fmaf(sm[sl][col][D + 1], ck, l);
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
+        for (int dt = 0; dt < D / 16; ++dt)
 #pragma unroll
           for (int i = 0; i < 4; ++i) o[dt][i] = fmaf(sm[sl][col][dt * 16 + 4 * h4 + i], ck, o[dt][i]);
       }
       m = mt;
     }
   }
-  if (!vrow || ks != 0) return;
+}
+
+// the lane's row of out: O / l as bf16 (zeros for a row that saw no key)
+template <int D>
+__device__ __forceinline__ void store_out(const AttnParams& a, const TileRows& tr,
+                                          const f32x4 (&o)[D / 16], float l) {
   const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-  __bf16* orow = a.out + (tok * a.H + head) * D + 4 * h4;
+  __bf16* orow = a.out + (tr.tok * a.H + tr.head) * D + 4 * tr.h4;
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) {
+  for (int dt = 0; dt < D / 16; ++dt) {
     bf16x4 v;
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = static_cast<__bf16>(o[dt][i] * inv);
     *reinterpret_cast<bf16x4*>(orow + dt * 16) = v;
   }
+}
+
+// Scoring chunks and prompt prefill (no plan, T > 1, >= 1024 cells): the workgroup's four
+// 16-row query tiles walk ONE key-block list -- the agent's prefix blocks, then the history
+// blocks of every stream the 64 rows touch, up to the furthest query's causal limit -- through
+// CS_ATTEND_STAGED (loading every block once per tile instead is 4x the L2 traffic for 64
+// rows of one stream).  Blocks outside a tile's own stream or causal range are masked per lane
+// (block_mask); the arithmetic of a block is attend_block's.
+// D = 256: one wave per SIMD (two: 208 B/lane of spills)
+template <int D>
+__global__ __launch_bounds__(kAttnThreads, D <= 128 ? 2 : 1)
+void prefix_attn_lds_kernel(AttnParams a) {
+  __shared__ __attribute__((aligned(16))) char lds[LdsTile<D>::kBytes];
+  const int bid = logical_block(a.swizzle);
+  const TileRows tr = tile_rows(a, bid / a.n_qg, bid % a.n_qg);
+  const HistBlocks hs = hist_blocks(a, tr.hb, tr.r0, tr.r0 + tr.nrows - 1);
+  const int nbp = (tr.pl + kKeyBlock - 1) / kKeyBlock;
+
+  bf16x8 qf[D / 32];
+  load_q<D>(a, tr, qf);
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.0f;
+
+  // the workgroup's key-block list
+  const KvBase kv = kv_base(a);
+  auto ref = [&](int it) {
+    return it < nbp ? prefix_block<D>(a, kv, tr, it) : hist_block<D>(a, kv, tr, hs, it - nbp);
+  };
+  CS_ATTEND_STAGED(D, a, tr, lds, nbp + hs.n, ref, qf, o, m, l);
+  combine_waves<D>(tr, lds, o, m, l);
+  if (tr.vrow && tr.ks == 0) store_out<D>(a, tr, o, l);
 }
 
 #ifdef CS_TRACE_ATTN
@@ -478,11 +584,11 @@ __device__ __forceinline__ void att_at(int i) {
 
 // Decode steps (a plan: few (group, head) cells, key splits): the agent's PREFIX blocks
 // are shared by the workgroup's four 16-row tiles, so the split's prefix blocks (split,
-// split + n_used, ...) are staged through LDS once per workgroup and attended by every
-// tile (loading each one per tile: 4x the load instructions, 68 % issue stalls at C5);
-// each tile's own streams' history blocks are then loaded per wave (item_ref, load_block).
+// split + n_used, ...) go through CS_ATTEND_STAGED, once per workgroup for every tile (loading
+// each one per tile: 4x the load instructions, 68 % issue stalls at C5); each tile's own
+// streams' history blocks are then loaded per wave (hist_block, load_block).
 // Every key block is attended exactly once per (query row, split).
-// two waves per SIMD at every D (D = 256: 237 VGPRs, no spills; 1 wave/SIMD before)
+// two waves per SIMD at every D (D = 256: no spills; 1 wave/SIMD before)
 //
 // ROWS (cs_prefix_attention_rows): the history is row-major for K AND V ([S][Hkv][ldh][D])
 // and slot j of stream s lives in stream row hrow[s][j] -- a beam inherits its parent's
@@ -498,64 +604,36 @@ void prefix_attn_plan_lds_kernel(AttnParams a) {
   using LT = LdsTile<D>;
   constexpr int NDS = D / 32;
   constexpr int NDT = D / 16;
-  constexpr int LDSW = D + 2;
-  constexpr int kBufBytes = 2 * LT::ELEMS * 2;
-  constexpr int kCombBytes = 3 * 16 * LDSW * 4;
   constexpr int kVImg = kKeyBlock * D * 2;            // ROWS: one wave's V image of a block
-  static_assert(kAttnThreads / 64 * kVImg <= kBufBytes, "the V images fit the prefix buffers");
-  __shared__ __attribute__((aligned(16))) char lds[kBufBytes > kCombBytes ? kBufBytes : kCombBytes];
-  __bf16* buf = reinterpret_cast<__bf16*>(lds);
-  auto sm = reinterpret_cast<float (*)[16][LDSW]>(lds);
+  static_assert(kAttnThreads / 64 * kVImg <= LT::kBufBytes, "the V images fit the prefix buffers");
+  __shared__ __attribute__((aligned(16))) char lds[LT::kBytes];
 
   ATT_T(if (threadIdx.x == 0) att_at(0);)
   // no plan (ROWS only): one workgroup per (group, head, query group), unsplit
   const int4 e = a.plan ? a.plan[blockIdx.x]
                         : int4{static_cast<int>(blockIdx.x) / a.n_qg, static_cast<int>(blockIdx.x) % a.n_qg,
                                1 << 8, 0};
-  const int pg = e.x, qg = e.y, split = e.z & 255, n_used = e.z >> 8, slot = e.w;
-  const int gi = pg / a.Hkv, g = pg % a.Hkv;
-  const int p = a.gpfx ? a.gpfx[gi] : gi;
-  const int M = a.n_str * a.T * a.rep;
-  const int r0 = qg * kGroupRows;
-  const int nrows = min(kGroupRows, M - r0);
-  const int n_qt = (nrows + 15) >> 4;
-  const int kw = n_qt == 1 ? 4 : (n_qt == 2 ? 2 : 1);
-  const int tid = threadIdx.x;
-  const int w = tid >> 6, lane = tid & 63;
-  const int qt = w % n_qt, ks = w / n_qt;
-  const bool active = ks < kw;
-  const int col = lane & 15, h4 = lane >> 4;
+  const int split = e.z & 255, n_used = e.z >> 8, slot = e.w;
+  const TileRows tr = tile_rows(a, e.x, e.y);
+  const int lane = tr.lane, w = tr.w, kw = tr.kw, ks = tr.ks;
+  const int col = tr.col, h4 = tr.h4;
+  const bool active = tr.active;
 
-  const int row = r0 + qt * 16 + col;
-  const bool vrow = active && row < M;
-  const int rr = row < M ? row : M - 1;
-  const int jh = rr % a.rep, bt = rr / a.rep;
-  const int t = bt % a.T, b = bt / a.T;
-  const int64_t tok = (static_cast<int64_t>(gi) * a.n_str + b) * a.T + t;
-  const int head = g * a.rep + jh;
-  const int hb = *a.hist_base;
-  const int pl = a.plen[p];
-  const int64_t po = a.poff[p];
-  const int hv = min(hb + t + 1, static_cast<int>(a.ldh));
-  const int kmin_pos = a.window > 0 ? pl + hb + t - a.window + 1 : INT32_MIN;
-
-  const int nbp = (pl + kKeyBlock - 1) / kKeyBlock;
+  const int nbp = (tr.pl + kKeyBlock - 1) / kKeyBlock;
   // this split's prefix blocks: split, split + n_used, ...  (workgroup-uniform)
   const int npi = nbp > split ? (nbp - split + n_used - 1) / n_used : 0;
-  ATT_T(if (tid == 0 && npi + hb + po >= 0) att_at(1);)
+  ATT_T(if (threadIdx.x == 0 && npi + tr.hb + tr.po >= 0) att_at(1);)
   // the tile's own streams' history blocks, per wave (split * kw + ks, + nslot, ...)
-  const int rt0 = r0 + qt * 16, rt1 = min(rt0 + 15, M - 1);
-  const int b_lo = (rt0 / a.rep) / a.T, b_hi = (rt1 / a.rep) / a.T;
-  const int t_hi = b_lo == b_hi ? (rt1 / a.rep) % a.T : a.T - 1;
-  const int nbh = (min(hb + t_hi + 1, static_cast<int>(a.ldh)) + kKeyBlock - 1) / kKeyBlock;
-  const int n_hist = (b_hi - b_lo + 1) * nbh;
+  const int rt0 = tr.r0 + tr.qt * 16;
+  const HistBlocks hs = hist_blocks(a, tr.hb, rt0, min(rt0 + 15, tr.M - 1));
+  const int n_hist = hs.n;
   const int nslot = n_used * kw;
   // ROWS: lane l's table entry (key l % 32) of history block ih; the first block's entry is
   // loaded here, its round trip hidden behind the prefix blocks, each later one during the
   // block before it
   auto hrow_of = [&](int ih) -> int32_t {
-    const int64_t sg = static_cast<int64_t>(gi) * a.n_str + b_lo + ih / nbh;
-    return a.hrow[sg * a.ldh + (ih % nbh) * kKeyBlock + (lane & 31)];
+    const int64_t sg = static_cast<int64_t>(tr.gi) * a.n_str + hs.b_lo + ih / hs.nbh;
+    return a.hrow[sg * a.ldh + (ih % hs.nbh) * kKeyBlock + (lane & 31)];
   };
   int32_t hcur = 0;
   if constexpr (ROWS) {
@@ -563,88 +641,25 @@ void prefix_attn_plan_lds_kernel(AttnParams a) {
   }
 
   bf16x8 qf[NDS];
-  {
-    const __bf16* qrow = a.q + (tok * a.H + head) * D + 8 * h4;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) {
-      if (vrow) {
-        qf[ds] = *reinterpret_cast<const bf16x8*>(qrow + ds * 32);
-      } else {
-#pragma unroll
-        for (int e2 = 0; e2 < 8; ++e2) qf[ds][e2] = static_cast<__bf16>(0.0f);
-      }
-    }
-  }
+  load_q<D>(a, tr, qf);
   f32x4 o[NDT];
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.0f;
 
   // ---- prefix blocks through LDS ----
-  u32x4 rk[LT::NCH], rv[LT::NCH];
-  auto fetch = [&](int j) {
-    const int64_t k0 = static_cast<int64_t>(g) * a.ldp + po + (split + j * n_used) * kKeyBlock;
-    const __bf16* ksrc = a.kp + k0 * D;
-    const __bf16* vsrc = a.vtp + k0 * D;
-#pragma unroll
-    for (int i = 0; i < LT::NCH; ++i) {
-      const int c = tid + kAttnThreads * i;
-      rk[i] = *reinterpret_cast<const u32x4*>(ksrc + c * 8);
-      rv[i] = *reinterpret_cast<const u32x4*>(vsrc + c * 8);
-    }
-  };
-  auto stage = [&](int sbuf) {
-    __bf16* kd = buf + sbuf * LT::ELEMS;
-    __bf16* vd = kd + LT::KELEMS;
-#pragma unroll
-    for (int i = 0; i < LT::NCH; ++i) {
-      const int c = tid + kAttnThreads * i;
-      *reinterpret_cast<u32x4*>(kd + (c / (D / 8)) * LT::KROW + (c % (D / 8)) * 8) = rk[i];
-      *reinterpret_cast<u32x4*>(vd + (c >> 2) * LT::VROW + (c & 3) * 8) = rv[i];
-    }
-  };
-  if (npi > 0) {
-    fetch(0);
-    stage(0);
-  }
-  __syncthreads();
-  for (int j = 0; j < npi; ++j) {
-    const bool more = j + 1 < npi;
-    if (more) fetch(j + 1);
-    if (active && (j % kw) == ks) {
-      const __bf16* kd = buf + (j & 1) * LT::ELEMS;
-      const __bf16* vd = kd + LT::KELEMS;
-      KeyBlock<D> f;
-#pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) {
-        f.k0[ds] = *reinterpret_cast<const bf16x8*>(kd + col * LT::KROW + ds * 32 + 8 * h4);
-        f.k1[ds] = *reinterpret_cast<const bf16x8*>(kd + (16 + col) * LT::KROW + ds * 32 + 8 * h4);
-      }
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        f.vlo[dt] = *reinterpret_cast<const bf16x4*>(vd + (dt * 16 + col) * LT::VROW + 4 * h4);
-        f.vhi[dt] = *reinterpret_cast<const bf16x4*>(vd + (dt * 16 + col) * LT::VROW + 16 + 4 * h4);
-      }
-      ItemRef r;
-      r.k = nullptr;
-      r.v = nullptr;
-      r.kb = (split + j * n_used) * kKeyBlock;
-      r.lim = vrow ? pl : 0;
-      r.pos0 = 0;
-      attend_block<D>(a, f, r, qf, kmin_pos, h4, o, m, l);
-    }
-    if (more) stage((j + 1) & 1);
-    __syncthreads();
-  }
+  const KvBase kv = kv_base(a);
+  auto ref = [&](int j) { return prefix_block<D>(a, kv, tr, split + j * n_used); };
+  CS_ATTEND_STAGED(D, a, tr, lds, npi, ref, qf, o, m, l);
 
-  ATT_T(if (tid == 0) att_at(2);)
+  ATT_T(if (threadIdx.x == 0) att_at(2);)
   if constexpr (!ROWS) {
     if (active) {
       for (int ih = split * kw + ks; ih < n_hist; ih += nslot) {
         KeyBlock<D> f;
-        const ItemRef r = item_ref(a, nbp + ih, nbp, nbh, b_lo, b, gi, g, po, pl, hv, vrow, col, h4, D);
-        load_block<D>(f, r);
-        attend_block<D>(a, f, r, qf, kmin_pos, h4, o, m, l);
+        const BlockRef r = hist_block<D>(a, kv, tr, hs, ih);
+        load_block<D>(f, r, col, h4);
+        attend_block<D>(a, f, r.mask, qf, tr.kmin_pos, h4, o, m, l);
       }
     }
   } else {
@@ -672,13 +687,13 @@ void prefix_attn_plan_lds_kernel(AttnParams a) {
     }
     if (active) {
       for (int ih = split * kw + ks; ih < n_hist; ih += nslot) {
-        const int bb = b_lo + ih / nbh;
-        const int kb = (ih % nbh) * kKeyBlock;
+        const BlockMask mk = hist_block<D>(a, kv, tr, hs, ih).mask;
+        const int kb = mk.kb;
         // keys the tile's rows can see (wave-uniform): only those are gathered
-        const int nvalid = min(kKeyBlock, min(hb + t_hi + 1, static_cast<int>(a.ldh)) - kb);
+        const int nvalid = min(kKeyBlock, hs.hlim - kb);
         const int n_instr = (nvalid + KPI - 1) / KPI;
         auto row_ptr = [&](const __bf16* base, int64_t srow, int key) {
-          return base + ((srow * a.Hkv + g) * a.ldh + kb + key) * D;
+          return base + ((srow * a.Hkv + tr.g) * a.ldh + kb + key) * D;
         };
         // stream rows of keys col, 16 + col (K fragments)
         const int64_t rk0 = __shfl(hcur, col, 64), rk1 = __shfl(hcur, 16 + col, 64);
@@ -716,68 +731,19 @@ void prefix_attn_plan_lds_kernel(AttnParams a) {
           f.vlo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4_ptr)(vimg + o2));
           f.vhi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4_ptr)(vimg + o2 + 32 * D));
         }
-        ItemRef r;
-        r.k = nullptr;
-        r.v = nullptr;
-        r.kb = kb;
-        r.lim = (vrow && bb == b) ? hv : 0;
-        r.pos0 = pl;
-        attend_block<D>(a, f, r, qf, kmin_pos, h4, o, m, l);
+        attend_block<D>(a, f, mk, qf, tr.kmin_pos, h4, o, m, l);
         hcur = hnext;
       }
     }
     __syncthreads();   // every wave's V image read before the combine reuses the LDS
   }
-  ATT_T(if (tid == 0 && l >= 0.0f) att_at(3);)
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
-
-  if (kw > 1) {
-    if (active && ks > 0) {
-      const int sl = w - n_qt;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sm[sl][col][dt * 16 + 4 * h4 + i] = o[dt][i];
-      if (h4 == 0) {
-        sm[sl][col][D] = m;
-        sm[sl][col][D + 1] = l;
-      }
-    }
-    __syncthreads();
-    if (active && ks == 0) {
-      float mt = m;
-      for (int k = 1; k < kw; ++k) mt = fmaxf(mt, sm[qt + n_qt * k - n_qt][col][D]);
-      const float c0 = mt == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(m - mt);
-      l *= c0;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) o[dt] *= c0;
-      for (int k = 1; k < kw; ++k) {
-        const int sl = qt + n_qt * k - n_qt;
-        const float mk = sm[sl][col][D];
-        const float ck = mt == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mk - mt);
-        l = fmaf(sm[sl][col][D + 1], ck, l);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) o[dt][i] = fmaf(sm[sl][col][dt * 16 + 4 * h4 + i], ck, o[dt][i]);
-      }
-      m = mt;
-    }
-  }
-  if (!vrow || ks != 0) return;
+  ATT_T(if (threadIdx.x == 0 && l >= 0.0f) att_at(3);)
+  combine_waves<D>(tr, lds, o, m, l);
+  if (!tr.vrow || ks != 0) return;
   if (n_used == 1) {
-    const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-    __bf16* orow = a.out + (tok * a.H + head) * D + 4 * h4;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      bf16x4 v;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = static_cast<__bf16>(o[dt][i] * inv);
-      *reinterpret_cast<bf16x4*>(orow + dt * 16) = v;
-    }
+    store_out<D>(a, tr, o, l);
   } else {
-    float* pr = a.part + (static_cast<int64_t>(slot) * kGroupRows + qt * 16 + col) * LDSW;
+    float* pr = a.part + (static_cast<int64_t>(slot) * kGroupRows + tr.qt * 16 + col) * LT::LDSW;
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
       *reinterpret_cast<f32x4*>(pr + dt * 16 + 4 * h4) = o[dt];
@@ -786,8 +752,10 @@ void prefix_attn_plan_lds_kernel(AttnParams a) {
       pr[D + 1] = l;
     }
   }
-  ATT_T(if (tid == 0) { __builtin_amdgcn_s_waitcnt(0); att_at(4); })
+  ATT_T(if (threadIdx.x == 0) { __builtin_amdgcn_s_waitcnt(0); att_at(4); })
 }
+
+#undef CS_ATTEND_STAGED
 
 // One workgroup per merge entry (kMergeRows rows of a split (group, head, query group)),
 // each wave two rows, one per 32-lane half: the half's lanes fold the splits' (m, l) into
@@ -878,16 +846,6 @@ struct RopeParams {
 // a per-thread loop over the heads serialised one memory round trip per head.
 constexpr int kRopeItems = 256;
 
-// fp32 -> bf16, round to nearest even, quiet NaN: the rounding of cs_gemm_bf16's split-K
-// fold (gemm.hip gto_bf), so a fold done here is bitwise the fold done there
-__device__ __forceinline__ __bf16 rope_to_bf(float f) {
-  const uint32_t u = __float_as_uint(f);
-  const uint16_t h = (u & 0x7fffffffu) > 0x7f800000u
-                         ? static_cast<uint16_t>((u >> 16) | 0x40)
-                         : static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  return __builtin_bit_cast(__bf16, h);
-}
-
 // FOLD: the projection arrives as a K-split GEMM's unfolded fp32 partials (r.part), summed
 // here in split order and rounded as cs_gemm_bf16's own fold would -- one launch and one
 // bf16 round trip fewer per layer, bitwise the same q / K / V.  NSP splits' loads are issued
@@ -950,8 +908,8 @@ __global__ __launch_bounds__(256) void rope_place_kernel(RopeParams r, int32_t n
       }
 #pragma unroll
       for (int e = 0; e < P; ++e) {
-        a[e] = rope_to_bf(fa[e]);
-        b[e] = rope_to_bf(fb[e]);
+        a[e] = to_bf16(fa[e]);
+        b[e] = to_bf16(fb[e]);
       }
     } else {
       const __bf16* src = row + static_cast<int64_t>(hh) * r.D + i0;
@@ -1337,65 +1295,6 @@ int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t 
                     const float* inv_freq, const int32_t* prefix_len, const int32_t* group_prefix,
                     int32_t n_groups, const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H,
                     int32_t Hkv, int32_t D, void* q_out, void* k_hist, void* vt_hist,
-                    int64_t ld_hist, int32_t v_rows, cs_stream_t stream);
-}  // namespace
-
-extern "C" {
-
-int cs_rope_place(const void* qkv, int64_t ld_qkv, const float* inv_freq, const int32_t* prefix_len,
-                  const int32_t* group_prefix, int32_t n_groups, const int32_t* hist_base,
-                  int32_t n_str, int32_t T, int32_t H, int32_t Hkv, int32_t D, void* q_out,
-                  void* k_hist, void* vt_hist, int64_t ld_hist, cs_stream_t stream) {
-  if (!qkv) return fail(CS_ERR_INVALID, "cs_rope_place: NULL pointer");
-  return rope_place_impl(qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix, n_groups,
-                         hist_base, n_str, T, H, Hkv, D, q_out, k_hist, vt_hist, ld_hist, 0, stream);
-}
-
-int cs_rope_place_rows(const void* qkv, int64_t ld_qkv, const float* inv_freq,
-                       const int32_t* prefix_len, const int32_t* group_prefix, int32_t n_groups,
-                       const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H, int32_t Hkv,
-                       int32_t D, void* q_out, void* k_hist, void* v_hist, int64_t ld_hist,
-                       cs_stream_t stream) {
-  if (!qkv) return fail(CS_ERR_INVALID, "cs_rope_place_rows: NULL pointer");
-  return rope_place_impl(qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix, n_groups,
-                         hist_base, n_str, T, H, Hkv, D, q_out, k_hist, v_hist, ld_hist, 1, stream);
-}
-
-int cs_rope_place_splitk(const float* part, int32_t splits, const float* inv_freq,
-                         const int32_t* prefix_len, const int32_t* group_prefix, int32_t n_groups,
-                         const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H,
-                         int32_t Hkv, int32_t D, void* q_out, void* k_hist, void* vt_hist,
-                         int64_t ld_hist, cs_stream_t stream) {
-  if (!part || splits < 1) return fail(CS_ERR_INVALID, "cs_rope_place_splitk: need partials, splits >= 1");
-  if (T >= 32) return fail(CS_ERR_INVALID, "cs_rope_place_splitk: T < 32 only (fold first for chunks)");
-  if (reinterpret_cast<uintptr_t>(part) % 16 || D % 16)
-    return fail(CS_ERR_INVALID, "cs_rope_place_splitk: partials 16-byte aligned, head_dim % 16 == 0");
-  return rope_place_impl(nullptr, static_cast<int64_t>(H + 2 * Hkv) * D, part, splits, inv_freq,
-                         prefix_len, group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
-                         k_hist, vt_hist, ld_hist, 0, stream);
-}
-
-int cs_rope_place_splitk_rows(const float* part, int32_t splits, const float* inv_freq,
-                              const int32_t* prefix_len, const int32_t* group_prefix,
-                              int32_t n_groups, const int32_t* hist_base, int32_t n_str, int32_t T,
-                              int32_t H, int32_t Hkv, int32_t D, void* q_out, void* k_hist,
-                              void* v_hist, int64_t ld_hist, cs_stream_t stream) {
-  if (!part || splits < 1) return fail(CS_ERR_INVALID, "cs_rope_place_splitk_rows: need partials, splits >= 1");
-  if (T >= 32) return fail(CS_ERR_INVALID, "cs_rope_place_splitk_rows: T < 32 only (fold first for chunks)");
-  if (reinterpret_cast<uintptr_t>(part) % 16 || D % 16)
-    return fail(CS_ERR_INVALID, "cs_rope_place_splitk_rows: partials 16-byte aligned, head_dim % 16 == 0");
-  return rope_place_impl(nullptr, static_cast<int64_t>(H + 2 * Hkv) * D, part, splits, inv_freq,
-                         prefix_len, group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
-                         k_hist, v_hist, ld_hist, 1, stream);
-}
-
-}  // extern "C"
-
-namespace {
-int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t splits,
-                    const float* inv_freq, const int32_t* prefix_len, const int32_t* group_prefix,
-                    int32_t n_groups, const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H,
-                    int32_t Hkv, int32_t D, void* q_out, void* k_hist, void* vt_hist,
                     int64_t ld_hist, int32_t v_rows, cs_stream_t stream) {
   if (n_groups < 0 || n_str < 0 || T < 0) return fail(CS_ERR_INVALID, "cs_rope_place: negative size");
   if (n_groups == 0 || n_str == 0 || T == 0) return CS_OK;
@@ -1458,4 +1357,63 @@ int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t 
                        static_cast<hipStream_t>(stream), r, static_cast<int32_t>(n_tiles));
   return check_launch("cs_rope_place");
 }
+
+// the checks the two split-K entry points share (`name`: the entry point's, for the messages)
+int rope_place_splitk_impl(const char* name, const float* part, int32_t splits, const float* inv_freq,
+                           const int32_t* prefix_len, const int32_t* group_prefix, int32_t n_groups,
+                           const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H, int32_t Hkv,
+                           int32_t D, void* q_out, void* k_hist, void* vt_hist, int64_t ld_hist,
+                           int32_t v_rows, cs_stream_t stream) {
+  const std::string nm(name);
+  if (!part || splits < 1) return fail(CS_ERR_INVALID, nm + ": need partials, splits >= 1");
+  if (T >= 32) return fail(CS_ERR_INVALID, nm + ": T < 32 only (fold first for chunks)");
+  if (reinterpret_cast<uintptr_t>(part) % 16 || D % 16)
+    return fail(CS_ERR_INVALID, nm + ": partials 16-byte aligned, head_dim % 16 == 0");
+  return rope_place_impl(nullptr, static_cast<int64_t>(H + 2 * Hkv) * D, part, splits, inv_freq,
+                         prefix_len, group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
+                         k_hist, vt_hist, ld_hist, v_rows, stream);
+}
 }  // namespace
+
+extern "C" {
+
+int cs_rope_place(const void* qkv, int64_t ld_qkv, const float* inv_freq, const int32_t* prefix_len,
+                  const int32_t* group_prefix, int32_t n_groups, const int32_t* hist_base,
+                  int32_t n_str, int32_t T, int32_t H, int32_t Hkv, int32_t D, void* q_out,
+                  void* k_hist, void* vt_hist, int64_t ld_hist, cs_stream_t stream) {
+  if (!qkv) return fail(CS_ERR_INVALID, "cs_rope_place: NULL pointer");
+  return rope_place_impl(qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix, n_groups,
+                         hist_base, n_str, T, H, Hkv, D, q_out, k_hist, vt_hist, ld_hist, 0, stream);
+}
+
+int cs_rope_place_rows(const void* qkv, int64_t ld_qkv, const float* inv_freq,
+                       const int32_t* prefix_len, const int32_t* group_prefix, int32_t n_groups,
+                       const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H, int32_t Hkv,
+                       int32_t D, void* q_out, void* k_hist, void* v_hist, int64_t ld_hist,
+                       cs_stream_t stream) {
+  if (!qkv) return fail(CS_ERR_INVALID, "cs_rope_place_rows: NULL pointer");
+  return rope_place_impl(qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix, n_groups,
+                         hist_base, n_str, T, H, Hkv, D, q_out, k_hist, v_hist, ld_hist, 1, stream);
+}
+
+int cs_rope_place_splitk(const float* part, int32_t splits, const float* inv_freq,
+                         const int32_t* prefix_len, const int32_t* group_prefix, int32_t n_groups,
+                         const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H,
+                         int32_t Hkv, int32_t D, void* q_out, void* k_hist, void* vt_hist,
+                         int64_t ld_hist, cs_stream_t stream) {
+  return rope_place_splitk_impl("cs_rope_place_splitk", part, splits, inv_freq, prefix_len,
+                                group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
+                                k_hist, vt_hist, ld_hist, 0, stream);
+}
+
+int cs_rope_place_splitk_rows(const float* part, int32_t splits, const float* inv_freq,
+                              const int32_t* prefix_len, const int32_t* group_prefix,
+                              int32_t n_groups, const int32_t* hist_base, int32_t n_str, int32_t T,
+                              int32_t H, int32_t Hkv, int32_t D, void* q_out, void* k_hist,
+                              void* v_hist, int64_t ld_hist, cs_stream_t stream) {
+  return rope_place_splitk_impl("cs_rope_place_splitk_rows", part, splits, inv_freq, prefix_len,
+                                group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
+                                k_hist, v_hist, ld_hist, 1, stream);
+}
+
+}  // extern "C"

@@ -153,6 +153,16 @@ __device__ __forceinline__ float load_one(const char* row, int64_t i) {
   }
 }
 
+// fp32 -> bf16 bits, round to nearest even, NaN kept quiet: the one rounding of the GEMM
+// epilogues and split-K folds (gemm.hip), the norms (norm.hip) and the fold inside
+// rope_place_kernel (attn.hip), so a fold done in one of them is bitwise the fold done in another
+__device__ __forceinline__ uint16_t bf16_bits(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40);
+  return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ __bf16 to_bf16(float f) { return __builtin_bit_cast(__bf16, bf16_bits(f)); }
+
 // Gemma-2 final-logit soft-capping, cap * tanh(x / cap), written through one exp2 and
 // the hardware reciprocal (1 ulp) so the vocab stream and the target gather use the
 // identical function:  r = 1 / (exp(2x/cap) + 1),  cap * tanh(x/cap) = cap - 2 cap r.

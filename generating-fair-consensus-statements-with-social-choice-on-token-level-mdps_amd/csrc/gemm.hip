@@ -42,12 +42,6 @@ constexpr int kGemmMaxMW = 9;       // 16-row tiles per wave: up to 288 rows per
 
 __device__ __forceinline__ float gbf(uint16_t v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
 
-__device__ __forceinline__ uint16_t gto_bf(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40);
-  return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 __device__ __forceinline__ float g_silu(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float g_gelu_tanh(float x) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
@@ -208,10 +202,10 @@ __global__ __launch_bounds__(kGemmThreads, 1) void ws_gemm_kernel(
       gu16x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float g = gbf(gto_bf(acc[i][0][e]));
-        const float u = gbf(gto_bf(acc[i][1][e]));
-        const uint16_t a = gto_bf(act ? g_gelu_tanh(g) : g_silu(g));
-        o[e] = gto_bf(gbf(a) * u);
+        const float g = gbf(bf16_bits(acc[i][0][e]));
+        const float u = gbf(bf16_bits(acc[i][1][e]));
+        const uint16_t a = bf16_bits(act ? g_gelu_tanh(g) : g_silu(g));
+        o[e] = bf16_bits(gbf(a) * u);
       }
       *reinterpret_cast<gu16x4*>(Y + m * ldy + f) = o;
     } else {
@@ -223,7 +217,7 @@ __global__ __launch_bounds__(kGemmThreads, 1) void ws_gemm_kernel(
         } else {
           gu16x4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = gto_bf(acc[i][j][e]);
+          for (int e = 0; e < 4; ++e) o[e] = bf16_bits(acc[i][j][e]);
           *reinterpret_cast<gu16x4*>(Y + m * ldy + n) = o;
         }
       }
@@ -511,10 +505,10 @@ __device__ __forceinline__ void ws2_store(const gf32x4 (&acc)[MT][NT], uint16_t*
         gu16x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float g = gbf(gto_bf(acc[i][jj][e]));
-          const float u = gbf(gto_bf(acc[i][kHalf + jj][e]));
-          const uint16_t a = gto_bf(act ? g_gelu_tanh(g) : g_silu(g));
-          o[e] = gto_bf(gbf(a) * u);
+          const float g = gbf(bf16_bits(acc[i][jj][e]));
+          const float u = gbf(bf16_bits(acc[i][kHalf + jj][e]));
+          const uint16_t a = bf16_bits(act ? g_gelu_tanh(g) : g_silu(g));
+          o[e] = bf16_bits(gbf(a) * u);
         }
         *reinterpret_cast<gu16x4*>(Y + m * ldy + f) = o;
       }
@@ -527,7 +521,7 @@ __device__ __forceinline__ void ws2_store(const gf32x4 (&acc)[MT][NT], uint16_t*
         } else {
           gu16x4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = gto_bf(acc[i][j][e]);
+          for (int e = 0; e < 4; ++e) o[e] = bf16_bits(acc[i][j][e]);
           *reinterpret_cast<gu16x4*>(Y + m * ldy + n) = o;
         }
       }
@@ -590,8 +584,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   gu16x8 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    o[e] = gto_bf(a[e]);
-    o[4 + e] = gto_bf(b[e]);
+    o[e] = bf16_bits(a[e]);
+    o[4 + e] = bf16_bits(b[e]);
   }
   *reinterpret_cast<gu16x8*>(Y + m * ldy + n) = o;
 }
@@ -699,10 +693,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void thin_gemm_kernel(
         gu16x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float gv = gbf(gto_bf(g[e]));
-          const float uv = gbf(gto_bf(up[e]));
-          const uint16_t a = gto_bf(act ? g_gelu_tanh(gv) : g_silu(gv));
-          o[e] = gto_bf(gbf(a) * uv);
+          const float gv = gbf(bf16_bits(g[e]));
+          const float uv = gbf(bf16_bits(up[e]));
+          const uint16_t a = bf16_bits(act ? g_gelu_tanh(gv) : g_silu(gv));
+          o[e] = bf16_bits(gbf(a) * uv);
         }
         *reinterpret_cast<gu16x4*>(Y + m * ldy + f0 + 4 * (lane >> 4)) = o;
       }
@@ -714,7 +708,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void thin_gemm_kernel(
       if (m < M) {
         gu16x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = gto_bf(a[e]);
+        for (int e = 0; e < 4; ++e) o[e] = bf16_bits(a[e]);
         *reinterpret_cast<gu16x4*>(Y + m * ldy + f0 + 16 * j + 4 * (lane >> 4)) = o;
       }
     }

@@ -21,13 +21,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf(uint16_t v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
 
-// fp32 -> bf16, round to nearest even (NaN kept quiet)
-__device__ __forceinline__ uint16_t to_bf(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40);
-  return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 constexpr int kNormThreads = 256;
 constexpr int kMaxSplits = 16;      // K-split partials folded by cs_add_rms_norm_splitk
 
@@ -110,8 +103,8 @@ __global__ __launch_bounds__(BLOCK) void add_rms_kernel(
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          bv[k][e] = to_bf(x0[e]);
-          bv[k][4 + e] = to_bf(x1[e]);
+          bv[k][e] = bf16_bits(x0[e]);
+          bv[k][4 + e] = bf16_bits(x1[e]);
         }
       } else if (b) {
         bv[k] = *reinterpret_cast<const u16x8*>(b + r * ldb + 8 * v);
@@ -144,7 +137,7 @@ __global__ __launch_bounds__(BLOCK) void add_rms_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float g = plus_one ? 1.0f + bf(g8[e]) : bf(g8[e]);
-          bv[k][e] = to_bf((bf(bv[k][e]) * inv_b) * g);
+          bv[k][e] = bf16_bits((bf(bv[k][e]) * inv_b) * g);
         }
       }
     }
@@ -156,7 +149,7 @@ __global__ __launch_bounds__(BLOCK) void add_rms_kernel(
     if (v < nv) {
       if (has_b) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) av[k][e] = to_bf(bf(av[k][e]) + bf(bv[k][e]));
+        for (int e = 0; e < 8; ++e) av[k][e] = bf16_bits(bf(av[k][e]) + bf(bv[k][e]));
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) ss = fmaf(bf(av[k][e]), bf(av[k][e]), ss);
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(BLOCK) void add_rms_kernel(
       for (int e = 0; e < 8; ++e) {
         const float g = plus_one ? 1.0f + bf(g8[e]) : bf(g8[e]);
         // Llama (F.rms_norm): x * inv * w, one rounding; Gemma: (x * inv) * (1 + w)
-        out[e] = to_bf((bf(av[k][e]) * inv) * g);
+        out[e] = bf16_bits((bf(av[k][e]) * inv) * g);
       }
       *reinterpret_cast<u16x8*>(y + r * ldy + 8 * v) = out;
     }
@@ -202,8 +195,8 @@ __global__ __launch_bounds__(kNormThreads) void gated_act_kernel(
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float x = bf(g[e]);
-    const uint16_t a = to_bf(act ? gelu_tanh_f(x) : silu_f(x));
-    o[e] = to_bf(bf(a) * bf(u[e]));
+    const uint16_t a = bf16_bits(act ? gelu_tanh_f(x) : silu_f(x));
+    o[e] = bf16_bits(bf(a) * bf(u[e]));
   }
   *reinterpret_cast<u16x8*>(out + r * ldo + j) = o;
 }

@@ -4,8 +4,10 @@ prompt) and the C2 scoring chunk.  Prints one JSON line per shape: us per launch
 merge) and the K/V bytes the launch must read (prefix once per (agent, head) + every
 stream's history).
 
-    python tools/attn_bench.py
-"""
+    python tools/attn_bench.py [--lib other/build.so] [--rows] [shape ...]
+
+--rows times the row-layout history (cs_prefix_attention_rows behind an identity slot table)
+instead of the V^T-tile one."""
 import importlib
 import json
 import os
@@ -23,6 +25,10 @@ if "--lib" in sys.argv:   # A/B another build of the library: --lib path/to/lib.
     del sys.argv[i:i + 2]
     _lib = importlib.import_module(PKG + "._lib")
     _lib.LIB_NAME = os.path.relpath(os.path.abspath(LIB), os.path.join(REPO, PKG))
+
+ROWS = "--rows" in sys.argv
+if ROWS:
+    sys.argv.remove("--rows")
 
 SHAPES = {
     # name: (n agent prefixes, agent len, ref len, n_str, T, H, Hkv, D, hist G, softcap)
@@ -62,7 +68,9 @@ def run(name, reps=50):
     S = n_grp * n_str
     ldh = ceil32(G + T)
     kh = torch.randn(S, Hkv, ldh, D, device=dev).to(bf)
-    vh = torch.randn(S, Hkv, ldh // 32, D, 32, device=dev).to(bf)
+    vh = (torch.randn(S, Hkv, ldh, D, device=dev) if ROWS else
+          torch.randn(S, Hkv, ldh // 32, D, 32, device=dev)).to(bf)
+    table = torch.arange(S, dtype=torch.int32, device=dev)[:, None].repeat(1, ldh) if ROWS else None
     q = torch.randn(S * T, H, D, device=dev).to(bf)
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)
     offt = torch.tensor(off, dtype=torch.int64, device=dev)
@@ -71,7 +79,8 @@ def run(name, reps=50):
 
     def go():
         ops.prefix_attention(q, kp, vt, offt, plen, max(lens), kh, vh, hb, n_str, T,
-                             scale=D ** -0.5, softcap=cap, out=out, prefix_len_host=lens)
+                             scale=D ** -0.5, softcap=cap, out=out, prefix_len_host=lens,
+                             hist_rows=table)
 
     for _ in range(5):
         go()
@@ -85,8 +94,8 @@ def run(name, reps=50):
     us = e0.elapsed_time(e1) * 1e3 / reps
     kv_bytes = 2 * Hkv * sum(lens) * D * 2 + 2 * S * Hkv * (G + T) * D * 2
     flops = 4 * S * T * H * D * (sum(lens) / n_grp + G + T / 2)
-    print(json.dumps({"shape": name, "lib": LIB or "tree", "us": us, "kv_bytes": kv_bytes,
-                      "gb_per_s": kv_bytes / us / 1e3, "tflops": flops / us / 1e6}), flush=True)
+    print(json.dumps({"shape": name, "route": "rows" if ROWS else "vt", "lib": LIB or "tree", "us": us,
+                      "kv_bytes": kv_bytes, "gb_per_s": kv_bytes / us / 1e3, "tflops": flops / us / 1e6}), flush=True)
 
 
 if __name__ == "__main__":
