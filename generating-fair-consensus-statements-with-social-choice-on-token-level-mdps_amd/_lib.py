@@ -19,6 +19,7 @@ LIB_NAME = "libconsensus_scoring.so"
 CS_F32, CS_BF16, CS_F16 = 0, 1, 2
 WELFARE_MIN, WELFARE_SUM, WELFARE_SUMLOG, WELFARE_MAX = 0, 1, 2, 3
 NONFINITE_SKIP, NONFINITE_REPLACE = 0, 1
+MAXIMIN_MAX_PIVOTS = 4096     # CS_MAXIMIN_MAX_PIVOTS
 
 EXPORTED = (
     "cs_version", "cs_last_error", "cs_workspace_size", "cs_logsoftmax_gather",
@@ -31,6 +32,7 @@ EXPORTED = (
     "cs_gemm_bf16_packed", "cs_gemm_pack", "cs_rope_place_splitk",
     "cs_add_rms_norm_splitk", "cs_prefix_attention_rows", "cs_rope_place_rows",
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
+    "cs_maximin_lottery",
 )
 
 
@@ -152,6 +154,9 @@ def load():
     L.cs_nash_lottery.restype = ctypes.c_int
     L.cs_lottery_policy.argtypes = [vp, i32, i32, i32, vp, vp]
     L.cs_lottery_policy.restype = ctypes.c_int
+    L.cs_maximin_lottery.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i32, i32, vp, vp, vp,
+                                     vp, vp]
+    L.cs_maximin_lottery.restype = ctypes.c_int
     _lib = L
     return L
 

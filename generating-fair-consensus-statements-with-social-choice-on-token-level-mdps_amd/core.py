@@ -3,8 +3,9 @@
 Same names, arguments and return types (NumPy in, NumPy out), but the per-step
 log-softmax + gather and the per-leaf folding run on the GPU through the C-ABI
 kernels (``ops.logsoftmax_gather`` -> ``ops.segment_reduce``), the point-mass
-welfare / selection through ``ops.welfare`` / ``ops.topk``, and the Nash-welfare
-lottery and its induced policy through ``ops.nash_lottery`` / ``ops.lottery_policy``.
+welfare / selection through ``ops.welfare`` / ``ops.topk``, the Nash-welfare
+lottery and its induced policy through ``ops.nash_lottery`` / ``ops.lottery_policy``, and
+the maximin lottery and the coalition-improvement metric through ``ops.maximin_lottery``.
 
 Reference (core.py):
   generate_params         49-56    (host RNG: parameters are inputs, not the hot path)
@@ -16,12 +17,20 @@ Reference (core.py):
   build_prefix_index      287-294
   induced_policy_rollout  297-332  -> cs_lottery_policy tables (induced_policy), host RNG draws
   utilitarian argmax      374-376  -> point_mass_select(U, "utilitarian")
+  egalitarian_lottery     171-206  -> cs_maximin_lottery (all agents, base 1): one optimal vertex
+  max_coalition_improvement 214-279 -> cs_maximin_lottery, every coalition's LP in one launch
+                                      (max_coalition_improvement_batch: many problems per launch;
+                                      maximin_certificate: the weak-duality bounds, host)
+  main's sweep            340-435  -> coalition_sweep (the numbers, no plot): one cs_nash_lottery
+                                      and one cs_maximin_lottery launch
 
-egalitarian_lottery and max_coalition_improvement (the HiGHS LPs, core.py:171-279) are
-not provided here.
+The two LPs are one matrix game, solved by a dual simplex instead of HiGHS: the optimal values
+agree with the reference's to its solver tolerance, the egalitarian lottery is an optimal vertex
+but not necessarily the same one.
 """
 from __future__ import annotations
 
+import functools
 import itertools
 
 import numpy as np
@@ -131,6 +140,163 @@ def nash_lottery_certificate(U, p):
     if np.any(a <= 0):
         return -np.inf, np.inf
     return float(np.sum(np.log(a))), float((U / a[:, None]).sum(0).max() - U.shape[0])
+
+
+MAX_COALITION_AGENTS = 16     # 2^16 - 1 = 65,535 coalitions (one workgroup each) per problem
+
+
+@functools.lru_cache(maxsize=None)
+def coalition_masks(n):
+    """All 2^n - 1 nonempty coalitions of n agents as bit masks (bit i = agent i), in the
+    reference's order: itertools.combinations by size (core.py:230-232)."""
+    if not 1 <= n <= MAX_COALITION_AGENTS:
+        raise ops.CSError(f"all coalitions are enumerated for at most {MAX_COALITION_AGENTS} agents "
+                          f"(got {n}); pass coalitions= for a chosen few")
+    out = [sum(1 << i for i in S) for r in range(1, n + 1)
+           for S in itertools.combinations(range(n), r)]
+    masks = np.array(out, dtype=np.uint64)
+    masks.setflags(write=False)
+    return masks
+
+
+def _as_masks(coalitions, n):
+    if coalitions is None:
+        return coalition_masks(n)
+    masks = []
+    for S in coalitions:
+        S = [int(i) for i in S]
+        if not S or min(S) < 0 or max(S) >= n or len(set(S)) != len(S):
+            raise ops.CSError(f"a coalition is a nonempty set of distinct agents below {n}, got {S}")
+        masks.append(sum(1 << i for i in S))
+    if not masks:
+        raise ops.CSError("coalitions= needs at least one coalition")
+    return np.array(masks, dtype=np.uint64)
+
+
+def _checked(pivots, what):
+    """Coalitions the kernel solved; one that ran out of pivots is an error, not a skip."""
+    if bool((pivots == -2).any()):
+        raise ops.CSError(f"{what}: a problem exhausted max_pivots (cs_maximin_lottery status -2)")
+    return pivots >= 0
+
+
+def egalitarian_lottery(U):
+    """The maximin lottery argmax_p min_i U_i . p on the GPU (core.py:171-206 contract), returns
+    p [m].  The LP's optimal value is unique, its p is not: this is one optimal vertex (that of a
+    dual simplex with lowest-index ties), not necessarily the one HiGHS returns.  A malformed
+    problem (a negative or non-finite utility, an all-zero agent) gets the uniform lottery, the
+    reference's fallback for a failed solve."""
+    U = np.asarray(U, dtype=np.float64)
+    if U.ndim != 2:
+        raise ops.CSError("egalitarian_lottery takes U [n, m]")
+    res = ops.maximin_lottery(torch.as_tensor(np.ascontiguousarray(U), device=_device()),
+                              with_lam=False)
+    if not bool(_checked(res["pivots"], "egalitarian_lottery")):
+        return np.ones(U.shape[1]) / U.shape[1]
+    return res["q"].cpu().numpy()
+
+
+def max_coalition_improvement_batch(Us, ps, coalitions=None):
+    """max_coalition_improvement of equal-shape problems [P, n, m] with lotteries [P, m] in ONE
+    launch (one workgroup per problem and coalition); returns the factors [P]."""
+    Us = np.ascontiguousarray(np.stack([np.asarray(U, dtype=np.float64) for U in Us]))
+    ps = np.stack([np.asarray(p, dtype=np.float64) for p in ps])
+    if Us.ndim != 3 or ps.shape != (Us.shape[0], Us.shape[2]):
+        raise ops.CSError("max_coalition_improvement_batch takes equal-shape [n, m] problems and "
+                          "one lottery [m] each")
+    masks = _as_masks(coalitions, Us.shape[1])
+    dev = _device()
+    base = np.stack([U @ p for U, p in zip(Us, ps)])          # core.py:226, problem by problem
+    res = ops.maximin_lottery(torch.as_tensor(Us, device=dev), torch.as_tensor(base, device=dev),
+                              masks, with_q=False, with_lam=False)
+    ok = _checked(res["pivots"], "max_coalition_improvement")
+    alpha = torch.where(ok, res["alpha"], torch.ones_like(res["alpha"]))
+    return alpha.max(dim=1).values.clamp_min(1.0).cpu().numpy()
+
+
+def max_coalition_improvement(U, p, coalitions=None):
+    """The core-violation metric of a lottery p (core.py:214-279 contract): the largest alpha
+    such that some coalition S can, with the share |S| / n of the probability, give every member
+    at least alpha times its utility under p; > 1 means p is blockable.  All 2^n - 1 coalitions
+    (n <= 16), or the given ``coalitions`` (iterables of agent indices), as one launch, one LP
+    each.  The maximum starts from 1.0; a coalition with a member of zero (or non-finite) base
+    utility is skipped, as the reference skips its unbounded LP.  Returns a float."""
+    U = np.asarray(U, dtype=np.float64)
+    p = np.asarray(p, dtype=np.float64)
+    if U.ndim != 2 or p.shape != (U.shape[1],):
+        raise ops.CSError("max_coalition_improvement takes U [n, m] and p [m]")
+    return float(max_coalition_improvement_batch(U[None], p[None], coalitions)[0])
+
+
+def maximin_certificate(U, q, lam, S=None, base=None):
+    """(lower, upper) of a lottery q and weights lam on the agents for coalition S (None: all)
+    and ``base`` (None: ones): lower = min_{i in S} (U_i . q) / base_i, upper = max_j sum_i lam_i
+    U[i, j] / base_i.  lower <= value <= upper by weak duality (lam >= 0 summing to 1 on S), so
+    equal bounds certify both (host, as nash_lottery_certificate)."""
+    U = np.asarray(U, dtype=np.float64)
+    S = list(range(U.shape[0])) if S is None else [int(i) for i in S]
+    b = np.ones(U.shape[0]) if base is None else np.asarray(base, dtype=np.float64)
+    M = U[S] / b[S, None]
+    return float((M @ np.asarray(q, dtype=np.float64)).min()), \
+        float((np.asarray(lam, dtype=np.float64)[S] @ M).max())
+
+
+def compute_utilities_fp64(v, w, rhos):
+    """compute_utilities for every rho of ``rhos`` with fp64 log-softmax steps (torch on the
+    device), returns U [len(rhos), n, m].  The coalition metric divides by utilities, so its
+    sweep needs them to more digits than the fp32 rows of cs_logsoftmax_gather carry."""
+    v = np.asarray(v, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    L, B, d = v.shape
+    dev = _device()
+    A = torch.as_tensor(np.array(enumerate_leaves(B, L), dtype=np.int64), device=dev)   # [m, L]
+    vt = torch.as_tensor(v, device=dev)
+    wt = torch.as_tensor(w, device=dev)
+    rt = torch.as_tensor(np.asarray(rhos, dtype=np.float64).reshape(-1), device=dev)
+    chosen = vt[torch.arange(L, device=dev)[None, :], A]                         # [m, L, d]
+    z = torch.cumsum(chosen, dim=1) - chosen
+    X = z[:, :, None, :] + vt[None, :, :, :]                                     # [m, L, B, d]
+    logits = rt[:, None, None, None, None] * torch.einsum("id,mtbd->imtb", wt, X)[None]
+    ls = torch.log_softmax(logits, dim=-1)                                       # [R, n, m, L, B]
+    idx = A[None, None, :, :, None].expand(ls.shape[0], ls.shape[1], -1, -1, 1)
+    logu = ls.gather(-1, idx).squeeze(-1).sum(dim=-1)                            # [R, n, m]
+    return torch.exp(logu - logu.max(dim=2, keepdim=True).values) + 1e-300       # core.py:94-99
+
+
+def sweep_lotteries(Us, max_iters=1500, tol=1e-11):
+    """The three lotteries the reference's sweep evaluates on every problem of Us [P, n, m]
+    (device): the Nash-welfare lottery (one cs_nash_lottery launch), the utilitarian point mass
+    and the uniform lottery (core.py:369-376).  Returns the problems three times over,
+    U3 [3 * P, n, m] in that order of lotteries, and base [3 * P, n] = U p."""
+    P, _, m = Us.shape
+    p_nw = ops.nash_lottery(Us, max_iters=max_iters, tol=tol)["p"]
+    p_util = torch.zeros_like(p_nw)
+    p_util[torch.arange(P, device=Us.device), Us.sum(dim=1).argmax(dim=1)] = 1.0
+    ps = torch.cat([p_nw, p_util, torch.full_like(p_nw, 1.0 / m)])
+    U3 = Us.repeat(3, 1, 1)
+    return U3, torch.einsum("pij,pj->pi", U3, ps)
+
+
+def coalition_sweep(B, L, d, n_agents, seeds, rho_grid, max_iters=1500, tol=1e-11):
+    """The numbers of the reference's experiment (core.py:340-435, no plotting): for every seed
+    and rho, the max coalition improvement of the Nash-welfare lottery, of the utilitarian point
+    mass and of the uniform lottery.  One cs_nash_lottery launch and one cs_maximin_lottery
+    launch for the whole sweep.  Returns {"seeds", "rho", "nash", "utilitarian", "uniform"},
+    the last three [len(seeds), len(rho_grid)]."""
+    seeds = [int(s) for s in seeds]
+    rho_grid = np.asarray(rho_grid, dtype=np.float64).reshape(-1)
+    masks = coalition_masks(int(n_agents))
+    Us = []
+    for seed in seeds:
+        v, w = generate_params(B, L, d, n_agents, seed=seed)
+        Us.append(compute_utilities_fp64(v, w, rho_grid))
+    U3, base = sweep_lotteries(torch.cat(Us).contiguous(), max_iters, tol)       # [3 * S * R, ..]
+    res = ops.maximin_lottery(U3, base, masks, with_q=False, with_lam=False)
+    ok = _checked(res["pivots"], "coalition_sweep")
+    alpha = torch.where(ok, res["alpha"], torch.ones_like(res["alpha"]))
+    top = alpha.max(dim=1).values.clamp_min(1.0).reshape(3, len(seeds), rho_grid.size).cpu().numpy()
+    return {"seeds": np.array(seeds), "rho": rho_grid, "nash": top[0], "utilitarian": top[1],
+            "uniform": top[2]}
 
 
 def induced_policy(p, B, L):

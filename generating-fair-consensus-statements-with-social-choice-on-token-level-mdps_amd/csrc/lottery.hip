@@ -1,5 +1,6 @@
 // lottery.hip — the Nash-welfare lottery over complete statements and the token policy it
-// induces (the reference's core.py:116-168 and 297-328), whole solves in one launch.
+// induces (the reference's core.py:116-168 and 297-328), and the maximin lottery / coalition
+// improvement LPs (core.py:171-279), whole solves in one launch.
 #include "cs_kernels.cuh"
 
 namespace {
@@ -308,6 +309,320 @@ __global__ __launch_bounds__(kPolicyBlock) void lottery_policy_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// cs_maximin_lottery: a revised dual simplex, one workgroup per (problem, coalition)
+// ---------------------------------------------------------------------------
+// The game value(M) = max_q min_{i in S} (M q)_i, M[l][j] = U[S_l][j] / base[S_l], is solved as
+// min 1.x s.t. M x >= 1, x >= 0 (x = q / value).  With slacks, -M x + s = -1 and the cost row
+// (1..1, 0..0) is dual-feasible from the all-slack basis, so there is no phase I.  The state is
+// the r x r basis inverse Binv (r = |S|), the basic values xB, the dual weights w (the slack
+// columns' reduced costs) and which column is basic in which row; the pivot row and the reduced
+// costs of the m lottery columns are formed from M on the fly, so nothing grows with m but M.
+// A pivot:
+//   1. leaving row k: the most negative xB, lowest row on ties (every thread scans the r values
+//      and gets the same k); none negative: optimal;
+//   2. every thread takes the nonbasic columns j = tid, tid + BLOCK, ... of the m lottery
+//      columns and then the r slacks: a_j = -sum_l Binv[k][l] M[l][j], d_j = max(1 - sum_l w[l]
+//      M[l][j], 0) (slack l: Binv[k][l] and w[l]), rows in index order, and keeps its best ratio
+//      d_j / -a_j over a_j < 0; the block's best (lowest j on ties: a total order, so the result
+//      does not depend on how it is reduced) is the entering column e;
+//   3. thread i < r forms t[i] = (Binv A_e)[i], and with it the new pivot row Binv[k][i] / t[k],
+//      the step xB[k] / t[k] and d_e (each recomputed per thread: the same bits);
+//   4. Binv (entries over the threads), xB and w are eliminated; thread 0 moves the basis.
+// The STAGED variant keeps M in LDS ([r][m]); the other divides U by base at every read: the
+// same operations in the same order, so the outputs are bitwise equal.  A one-column problem has
+// one lottery and is answered without a pivot.  No atomics, no host sync.
+constexpr int kMmxBasicWords = (kLotMaxM + kLotMaxA + 31) / 32;
+constexpr int kMmxNarrowM = 128;              // up to this many columns: one wave per workgroup
+
+struct MmxSmem {
+  double xB[kLotMaxA], w[kLotMaxA], t[kLotMaxA], row[kLotMaxA], bs[kLotMaxA];
+  double wg[16];                  // one best ratio per wave
+  int32_t wj[16];
+  unsigned long long wpos[16];    // per wave: the rows of M that hold a positive entry
+  int32_t basis[kLotMaxA], agent[kLotMaxA];
+  uint32_t basic[kMmxBasicWords];
+  double sx, sw;
+};
+
+// (ratio, j) ordered by ratio ascending, then j ascending
+__device__ __forceinline__ bool mmx_better(double g, int32_t j, double g0, int32_t j0) {
+  return g < g0 || (g == g0 && j < j0);
+}
+
+template <int BLOCK, bool STAGED>
+__global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
+    const double* __restrict__ U, int32_t A, int32_t m, int64_t ldu, int64_t ldp,
+    const double* __restrict__ base, const unsigned long long* __restrict__ masks, int32_t C,
+    int32_t max_pivots, double* __restrict__ out_alpha, double* __restrict__ out_q,
+    double* __restrict__ out_lambda, int32_t* __restrict__ out_pivots) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ MmxSmem S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t prob = blockIdx.x / C;
+  const int32_t coal = blockIdx.x % C;
+  const double* Ug = U + prob * ldp;
+  const int64_t slot = prob * C + coal;
+
+  const unsigned long long all = A == 64 ? ~0ull : (1ull << A) - 1ull;
+  const unsigned long long mask = (masks ? masks[coal] : all) & all;
+  const int32_t r = __popcll(mask);
+  const int32_t ldb = r | 1;      // odd row stride: a column of Binv spreads over the banks
+  double* Binv = sm;
+  const double* smM = sm + static_cast<int64_t>(A) * (A | 1);   // where the host put M's share
+
+  int bad = r == 0;
+  if (tid < 64 && ((mask >> tid) & 1ull)) {
+    const int32_t l = __popcll(mask & ((1ull << tid) - 1ull));
+    const double b = base ? base[prob * A + tid] : 1.0;
+    S.agent[l] = tid;
+    S.bs[l] = b;
+    if (!(b > 0.0 && b < INFINITY)) bad = 1;
+  }
+  __syncthreads();
+  // the problem's entries checked (all A rows), the coalition's rows of M checked and staged
+  unsigned long long pos = 0;
+  for (int32_t j = tid; j < m; j += BLOCK) {
+    for (int32_t i = 0; i < A; ++i) {
+      const double u = Ug[i * ldu + j];
+      if (!(u >= 0.0) || u == INFINITY) bad = 1;
+    }
+    for (int32_t l = 0; l < r; ++l) {
+      const double v = Ug[S.agent[l] * ldu + j] / S.bs[l];
+      if (v > 0.0) pos |= 1ull << l;
+      if (v == INFINITY) bad = 1;          // U / base overflowed
+      if (STAGED) sm[static_cast<int64_t>(A) * (A | 1) + static_cast<int64_t>(l) * m + j] = v;
+    }
+  }
+  for (int k = 1; k < 64; k <<= 1) pos |= __shfl_xor(pos, k, 64);
+  if (lane == 0) S.wpos[wave] = pos;
+  bad = __syncthreads_or(bad);
+  for (int w = 0; w < BLOCK / 64; ++w) pos |= S.wpos[w];
+  const unsigned long long rows = r == 64 ? ~0ull : (1ull << r) - 1ull;
+  if (pos != rows) bad = 1;                // a member whose row of M is all zero (block-uniform)
+
+  auto M = [&](int32_t l, int32_t j) -> double {
+    return STAGED ? smM[static_cast<int64_t>(l) * m + j] : Ug[S.agent[l] * ldu + j] / S.bs[l];
+  };
+  auto is_basic = [&](int32_t j) -> bool { return (S.basic[j >> 5] >> (j & 31)) & 1u; };
+
+  int32_t status = bad ? -1 : 0;           // block-uniform from here on
+  if (!bad && m == 1) {
+    // one column: q = (1), value = min_l M[l][0], the weight on the lowest row that attains it
+    if (tid == 0) {
+      int32_t kmin = 0;
+      double vmin = M(0, 0);
+      for (int32_t l = 1; l < r; ++l) {
+        const double v = M(l, 0);
+        if (v < vmin) {
+          vmin = v;
+          kmin = l;
+        }
+      }
+      out_alpha[slot] = (static_cast<double>(r) / static_cast<double>(A)) * vmin;
+      if (out_q) out_q[slot] = 1.0;
+      if (out_lambda)
+        for (int32_t i = 0; i < A; ++i) out_lambda[slot * A + i] = i == S.agent[kmin] ? 1.0 : 0.0;
+      out_pivots[slot] = 0;
+    }
+    return;
+  }
+  if (!bad) {
+    for (int32_t idx = tid; idx < r * r; idx += BLOCK) {
+      const int32_t i = idx / r, l = idx - i * r;
+      Binv[i * ldb + l] = i == l ? 1.0 : 0.0;
+    }
+    if (tid < r) {
+      S.xB[tid] = -1.0;
+      S.w[tid] = 0.0;
+      S.basis[tid] = m + tid;
+    }
+    for (int32_t wi = tid; wi < (m + r + 31) / 32; wi += BLOCK) {
+      uint32_t v = 0;
+      for (int b = 0; b < 32; ++b) {
+        const int32_t j = wi * 32 + b;
+        if (j >= m && j < m + r) v |= 1u << b;
+      }
+      S.basic[wi] = v;
+    }
+    int32_t pivots = 0;
+    for (;;) {
+      __syncthreads();
+      int32_t k = 0;
+      double xk = S.xB[0];
+      for (int32_t i = 1; i < r; ++i) {
+        const double x = S.xB[i];
+        if (x < xk) {
+          xk = x;
+          k = i;
+        }
+      }
+      if (!(xk < 0.0)) {
+        status = pivots;
+        break;
+      }
+      if (pivots >= max_pivots) {
+        status = -2;
+        break;
+      }
+      // the ratio test over this thread's columns
+      const double* rho = Binv + k * ldb;
+      double bg = INFINITY;
+      int32_t bj = 0x7fffffff;
+      for (int32_t j = tid; j < m + r; j += BLOCK) {
+        if (is_basic(j)) continue;
+        double a, d;
+        if (j < m) {
+          double acc_a = 0.0, acc_d = 0.0;
+          for (int32_t l = 0; l < r; ++l) {
+            const double v = M(l, j);
+            acc_a += rho[l] * v;
+            acc_d += S.w[l] * v;
+          }
+          a = -acc_a;
+          d = fmax(1.0 - acc_d, 0.0);
+        } else {
+          a = rho[j - m];
+          d = S.w[j - m];
+        }
+        if (a < 0.0) {
+          const double g = d / -a;
+          if (mmx_better(g, j, bg, bj)) {
+            bg = g;
+            bj = j;
+          }
+        }
+      }
+      for (int s = 1; s < 64; s <<= 1) {
+        const double og = shfl_xor_f64(bg, s);
+        const int32_t oj = __shfl_xor(bj, s, 64);
+        if (mmx_better(og, oj, bg, bj)) {
+          bg = og;
+          bj = oj;
+        }
+      }
+      if (lane == 0) {
+        S.wg[wave] = bg;
+        S.wj[wave] = bj;
+      }
+      __syncthreads();
+      bg = S.wg[0];
+      bj = S.wj[0];
+      for (int w = 1; w < BLOCK / 64; ++w) {
+        if (mmx_better(S.wg[w], S.wj[w], bg, bj)) {
+          bg = S.wg[w];
+          bj = S.wj[w];
+        }
+      }
+      const int32_t e = bj;
+      if (e >= m + r) {                    // no column can enter: rounding only, the LP is feasible
+        status = -2;
+        break;
+      }
+      // the entering column in the basis' coordinates, the new pivot row, the step
+      double theta = 0.0, de = 0.0;
+      if (tid < r) {
+        double ti, piv;
+        if (e < m) {
+          double acc_t = 0.0, acc_p = 0.0, acc_d = 0.0;
+          for (int32_t l = 0; l < r; ++l) {
+            const double v = M(l, e);
+            acc_t += Binv[tid * ldb + l] * -v;
+            acc_p += rho[l] * -v;
+            acc_d += S.w[l] * v;
+          }
+          ti = acc_t;
+          piv = acc_p;
+          de = fmax(1.0 - acc_d, 0.0);
+        } else {
+          ti = Binv[tid * ldb + (e - m)];
+          piv = rho[e - m];
+          de = S.w[e - m];
+        }
+        theta = xk / piv;
+        S.t[tid] = ti;
+        S.row[tid] = rho[tid] / piv;
+      }
+      __syncthreads();
+      for (int32_t idx = tid; idx < r * r; idx += BLOCK) {
+        const int32_t i = idx / r, l = idx - i * r;
+        Binv[i * ldb + l] = i == k ? S.row[l] : Binv[i * ldb + l] - S.t[i] * S.row[l];
+      }
+      if (tid < r) {
+        S.xB[tid] = tid == k ? theta : S.xB[tid] - S.t[tid] * theta;
+        S.w[tid] = fmax(S.w[tid] - de * S.row[tid], 0.0);
+      }
+      if (tid == 0) {
+        const int32_t out = S.basis[k];
+        S.basic[out >> 5] &= ~(1u << (out & 31));
+        S.basic[e >> 5] |= 1u << (e & 31);
+        S.basis[k] = e;
+      }
+      ++pivots;
+    }
+  }
+  if (status >= 0) {
+    if (tid == 0) {
+      double sx = 0.0, sw = 0.0;
+      for (int32_t i = 0; i < r; ++i)
+        if (S.basis[i] < m) sx += S.xB[i];
+      for (int32_t i = 0; i < r; ++i) sw += S.w[i];
+      S.sx = sx;
+      S.sw = sw;
+    }
+    __syncthreads();
+    if (!(S.sx > 0.0 && S.sx < INFINITY && S.sw > 0.0 && S.sw < INFINITY)) status = -2;
+  }
+  if (status < 0) {
+    const double nan = __builtin_nan("");
+    if (out_q)
+      for (int32_t j = tid; j < m; j += BLOCK) out_q[slot * m + j] = nan;
+    if (out_lambda && tid < A) out_lambda[slot * A + tid] = nan;
+    if (tid == 0) {
+      out_alpha[slot] = nan;
+      out_pivots[slot] = status;
+    }
+    return;
+  }
+  const double sx = S.sx, sw = S.sw;
+  if (out_q) {
+    for (int32_t j = tid; j < m; j += BLOCK) {
+      double q = 0.0;
+      if (is_basic(j))
+        for (int32_t i = 0; i < r; ++i)
+          if (S.basis[i] == j) q = S.xB[i] / sx;
+      out_q[slot * m + j] = q;
+    }
+  }
+  if (out_lambda && tid < A) {
+    double lam = 0.0;
+    if ((mask >> tid) & 1ull) lam = S.w[__popcll(mask & ((1ull << tid) - 1ull))] / sw;
+    out_lambda[slot * A + tid] = lam;
+  }
+  if (tid == 0) {
+    out_alpha[slot] = (static_cast<double>(r) / static_cast<double>(A)) * (1.0 / sx);
+    out_pivots[slot] = status;
+  }
+}
+
+template <int BLOCK, bool STAGED>
+void launch_maximin(hipStream_t st, int64_t grid, size_t lds, const double* U, int32_t A, int32_t m,
+                    int64_t ldu, int64_t ldp, const double* base, const uint64_t* masks, int32_t C,
+                    int32_t max_pivots, double* out_alpha, double* out_q, double* out_lambda,
+                    int32_t* out_pivots) {
+  if (lds > 64 * 1024) {
+    // more dynamic LDS than the default launch limit: raised once per process
+    static const hipError_t raised = hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&maximin_lottery_kernel<BLOCK, STAGED>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLotLdsBytes));
+    (void)raised;  // a refusal shows as the launch's own error
+  }
+  hipLaunchKernelGGL((maximin_lottery_kernel<BLOCK, STAGED>), dim3(static_cast<uint32_t>(grid)),
+                     dim3(BLOCK), lds, st, U, A, m, ldu, ldp, base,
+                     reinterpret_cast<const unsigned long long*>(masks), C, max_pivots, out_alpha,
+                     out_q, out_lambda, out_pivots);
+}
+
 // B^L if it is <= limit, else -1 (no overflow: stops at the first product past the limit)
 int64_t pow_limited(int32_t B, int32_t L, int64_t limit) {
   int64_t n = 1;
@@ -362,6 +677,61 @@ int cs_nash_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ld
     else go(integral_constant<int, 256>{}, std::false_type{});
   }
   return check_launch("cs_nash_lottery");
+}
+
+int cs_maximin_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ldu,
+                       int64_t ldp_problem, const double* base, const uint64_t* masks_host,
+                       const uint64_t* masks, int32_t C, int32_t max_pivots, double* out_alpha,
+                       double* out_q, double* out_lambda, int32_t* out_pivots, cs_stream_t stream) {
+  const std::string w = "cs_maximin_lottery: ";
+  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
+  if (A < 1 || A > kLotMaxA) return fail(CS_ERR_INVALID, w + "need 1 <= A <= 64");
+  if (m < 1 || m > kLotMaxM) return fail(CS_ERR_INVALID, w + "need 1 <= m <= 16384");
+  if (ldu < m) return fail(CS_ERR_INVALID, w + "need ldu >= m");
+  if (ldp_problem < static_cast<int64_t>(A - 1) * ldu + m)
+    return fail(CS_ERR_INVALID, w + "problems overlap (need ldp_problem >= (A - 1) * ldu + m)");
+  if (max_pivots < 0) return fail(CS_ERR_INVALID, w + "need max_pivots >= 0");
+  if (C < 1) return fail(CS_ERR_INVALID, w + "need C >= 1");
+  if ((masks_host == nullptr) != (masks == nullptr))
+    return fail(CS_ERR_INVALID, w + "masks_host and masks come together (or both NULL)");
+  if (!masks && C != 1) return fail(CS_ERR_INVALID, w + "NULL masks mean one coalition (C = 1)");
+  if (masks_host) {
+    const uint64_t all = A == 64 ? ~uint64_t{0} : (uint64_t{1} << A) - 1;
+    for (int32_t c = 0; c < C; ++c) {
+      if (masks_host[c] == 0) return fail(CS_ERR_INVALID, w + "empty coalition mask");
+      if (masks_host[c] & ~all) return fail(CS_ERR_INVALID, w + "coalition mask names an agent >= A");
+    }
+  }
+  const int64_t grid = static_cast<int64_t>(P) * C;
+  if (int rc = check_grid("cs_maximin_lottery", grid)) return rc;
+  if (P == 0) return CS_OK;
+  if (!U || !out_alpha || !out_pivots) return fail(CS_ERR_INVALID, w + "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(U) % 8 != 0 || reinterpret_cast<uintptr_t>(base) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(masks) % 8 != 0 || reinterpret_cast<uintptr_t>(out_alpha) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(out_q) % 8 != 0 || reinterpret_cast<uintptr_t>(out_lambda) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(out_pivots) % 4 != 0)
+    return fail(CS_ERR_INVALID, w + "U, base, masks and the fp64 outputs must be 8-byte aligned");
+  // Binv's share is sized by A (a coalition has at most A rows); M is staged whenever it fits too
+  const size_t binv_bytes = static_cast<size_t>(A) * (A | 1) * sizeof(double);
+  const size_t m_bytes = static_cast<size_t>(A) * m * sizeof(double);
+  const bool staged = binv_bytes + m_bytes <= kLotLdsBytes;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto go = [&](auto block, auto stg) {
+    launch_maximin<decltype(block)::value, decltype(stg)::value>(
+        st, grid, binv_bytes + (decltype(stg)::value ? m_bytes : 0), U, A, m, ldu, ldp_problem, base,
+        masks, C, max_pivots, out_alpha, out_q, out_lambda, out_pivots);
+  };
+  using std::integral_constant;
+  if (m <= kMmxNarrowM) {
+    go(integral_constant<int, 64>{}, std::true_type{});   // 64 x 65 + 64 x 128 doubles always fit
+  } else if (m <= kLotWideM) {
+    if (staged) go(integral_constant<int, 256>{}, std::true_type{});
+    else go(integral_constant<int, 256>{}, std::false_type{});
+  } else {
+    if (staged) go(integral_constant<int, 1024>{}, std::true_type{});
+    else go(integral_constant<int, 1024>{}, std::false_type{});
+  }
+  return check_launch("cs_maximin_lottery");
 }
 
 int cs_lottery_policy(const double* p, int32_t P, int32_t B, int32_t L, double* out_policy,

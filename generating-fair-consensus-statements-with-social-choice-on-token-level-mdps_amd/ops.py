@@ -13,6 +13,7 @@ import collections
 import contextlib
 import ctypes
 import json
+import operator
 import os
 import threading
 from typing import Dict, NamedTuple, Optional, Sequence
@@ -1090,6 +1091,90 @@ def nash_lottery(U: torch.Tensor, max_iters: int = 1000, tol: float = 1e-10,
                            iters.data_ptr(), _stream())
     _lib.check(rc, "cs_nash_lottery")
     out = {"p": p, "a": a, "F": F, "gap": gap, "iters": iters}
+    return out if batched else {k: v[0] for k, v in out.items()}
+
+
+MAXIMIN_MAX_PIVOTS = _lib.MAXIMIN_MAX_PIVOTS
+_mask_cache: "collections.OrderedDict" = collections.OrderedDict()   # (device, bytes) -> device copy
+
+
+def coalition_masks(masks, A: int) -> np.ndarray:
+    """masks (ints, or a uint64 / int64 array) as the uint64 array the entry point takes, checked:
+    every mask is a nonempty set of agents below A."""
+    try:
+        ints = [operator.index(x) for x in np.asarray(masks, dtype=object).reshape(-1)]
+    except (TypeError, ValueError) as e:
+        raise CSError(f"coalition masks must be integers: {e}") from e
+    if not ints:
+        raise CSError("need at least one coalition mask")
+    if any(x <= 0 or x >> A for x in ints):
+        raise CSError(f"every coalition mask must be a nonempty set of agents below {A}")
+    return np.array(ints, dtype=np.uint64)
+
+
+def _masks_on(device: torch.device, host: np.ndarray) -> torch.Tensor:
+    key = (str(device), host.tobytes())
+    t = _mask_cache.get(key)
+    if t is None:
+        t = torch.as_tensor(host.view(np.int64), device=device)
+        _mask_cache[key] = t
+        while len(_mask_cache) > 8:
+            _mask_cache.popitem(last=False)
+    else:
+        _mask_cache.move_to_end(key)
+    return t
+
+
+def maximin_lottery(U: torch.Tensor, base: Optional[torch.Tensor] = None, masks=None,
+                    max_pivots: int = MAXIMIN_MAX_PIVOTS, *, with_q: bool = True,
+                    with_lam: bool = True) -> Dict[str, torch.Tensor]:
+    """The matrix game max_q min_{i in S} (U_i . q) / base_i of every (problem, coalition) in one
+    launch (cs_maximin_lottery): the maximin lottery and the coalition-improvement factor.
+
+    U [A, m] or [P, A, m] float64 with unit column stride (A <= 64, m <= 16384); base [A] or
+    [P, A] float64 (None: ones); masks: C coalition bit masks (bit i = agent i) as host integers,
+    shared by all problems (None: one coalition of all agents).
+    Returns {"alpha": |S| / A * value, "q": the optimal lottery [.., m], "lam": the dual weights
+    on the agents [.., A], "pivots": int32}, each with leading dimensions [P] (batched U) and [C]
+    (masks given).  pivots = -1 and NaN: a negative or non-finite utility in the problem, a
+    member's base not finite and positive, or a member's row all zero; -2 and NaN: max_pivots
+    exhausted.  with_q / with_lam = False leave that output out.
+    Restates the LPs of egalitarian_lottery and max_coalition_improvement (core.py:171-279)."""
+    L = _lib.load()
+    if U.dim() not in (2, 3) or U.dtype != torch.float64 or (U.stride(-1) != 1 and U.shape[-1] > 1):
+        raise CSError("U must be [A, m] or [P, A, m] float64 with unit column stride")
+    _require_cuda(U, base)
+    batched = U.dim() == 3
+    P = U.shape[0] if batched else 1
+    A, m = U.shape[-2], U.shape[-1]
+    ldu = U.stride(-2) if A > 1 else m
+    ldp = U.stride(0) if batched and P > 1 else max(A, 1) * ldu
+    dev = U.device
+    if base is not None:
+        if base.dtype != torch.float64 or tuple(base.shape) != ((P, A) if batched else (A,)):
+            raise CSError("base must be float64 of shape [A] (or [P, A] for batched U)")
+        base = base.contiguous()
+    if masks is None:
+        C, mh, md = 1, None, None
+    else:
+        host = coalition_masks(masks, A)
+        C, mh, md = host.size, host.ctypes.data, _masks_on(dev, host).data_ptr()
+    alpha = torch.empty((P, C), dtype=torch.float64, device=dev)
+    q = torch.empty((P, C, m), dtype=torch.float64, device=dev) if with_q else None
+    lam = torch.empty((P, C, A), dtype=torch.float64, device=dev) if with_lam else None
+    pivots = torch.empty((P, C), dtype=torch.int32, device=dev)
+    rc = L.cs_maximin_lottery(U.data_ptr(), P, A, m, ldu, ldp,
+                              None if base is None else base.data_ptr(), mh, md, C, int(max_pivots),
+                              alpha.data_ptr(), None if q is None else q.data_ptr(),
+                              None if lam is None else lam.data_ptr(), pivots.data_ptr(), _stream())
+    _lib.check(rc, "cs_maximin_lottery")
+    out = {"alpha": alpha, "pivots": pivots}
+    if with_q:
+        out["q"] = q
+    if with_lam:
+        out["lam"] = lam
+    if masks is None:
+        out = {k: v[:, 0] for k, v in out.items()}
     return out if batched else {k: v[0] for k, v in out.items()}
 
 

@@ -544,6 +544,63 @@ int cs_nash_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ld
                     cs_stream_t stream);
 
 /*
+ * cs_maximin_lottery — the maximin (egalitarian) lottery and the coalition-improvement factor,
+ * for P problems x C coalitions in one launch, one workgroup per (problem, coalition).  For a
+ * coalition S and base > 0 let M[i][j] = U[i][j] / base[i], i in S.  The workgroup solves the
+ * matrix game value(M) = max_{q in simplex} min_{i in S} (M q)_i and returns
+ *   out_alpha = |S| / A * value(M),
+ * which is the optimum of the reference's LP "maximise alpha s.t. U_i . p' >= alpha * base_i
+ * (i in S), sum p' = |S| / A, p' >= 0" (substitute p' = |S| / A * q); with S = all agents and
+ * base = 1 it is the egalitarian LP and q the maximin lottery.
+ *
+ * Method: with x = q / value the game is min 1.x s.t. M x >= 1, x >= 0, dual-feasible from the
+ * all-slack basis, solved by a revised dual simplex: leaving row the most negative basic value;
+ * entering column the smallest ratio (reduced cost) / -(pivot-row entry) over the negative
+ * entries of the pivot row; lowest index on every tie (the m lottery columns before the
+ * slacks).  Only the |S| x |S| basis inverse is carried; the pivot row and the reduced costs
+ * are formed from M every pivot.  All fp64.  A one-column problem (m = 1) has one lottery and is
+ * answered without a pivot.  There is no fallback rule against cycling: max_pivots bounds the
+ * work.  CS_MAXIMIN_MAX_PIVOTS is the default cap: every pivot visits a basis, the most seen
+ * over the 1,713 LPs of the recorded 6 x 81 sweep problems was 19 and 259 for a 64 x 300 problem
+ * with all 64 agents, so 4096 is generous but finite.
+ *
+ * U, P, A, m, ldu, ldp_problem: as for cs_nash_lottery (1 <= A <= 64, 1 <= m <= 16384).
+ * base [P][A]: nullable = all ones.
+ * masks_host / masks: the same C 64-bit coalition masks (bit i = agent i), shared by all
+ * problems, once in HOST memory (checked here: an empty mask or a bit at or above A is
+ * CS_ERR_INVALID) and once in DEVICE memory (read by the kernel, which ignores bits at or above
+ * A and gives an empty mask status -1, so a device copy that differs cannot read out of bounds).
+ * Both NULL: one coalition of all agents (C = 1).  P * C <= 2^31 - 1.
+ *
+ * LDS: the basis inverse (A * (A | 1) * 8 bytes) always; M is staged too when both fit the
+ * 147456 bytes the kernel may take, (A * (A | 1) + A * m) * 8 <= 147456.  Above that the kernel
+ * reads U from global memory (L2) and divides by base at every use: the same operations in the
+ * same order, so the result does not depend on which path ran.  Workgroups of 64 threads up to
+ * m = 128, 256 up to m = 4096, 1024 above.
+ *
+ * out_alpha [P][C]; nullable out_q [P][C][m] (>= 0, sums to 1, exact zeros off the basis);
+ * nullable out_lambda [P][C][A], the dual weights (>= 0, zero outside S, sum to 1):
+ * min_{i in S} (M q)_i <= value <= max_j (lambda M)_j certifies the result by weak duality;
+ * out_pivots [P][C] the pivots taken.
+ * out_pivots = -1 and NaN in the other outputs of that (problem, coalition): the problem holds
+ * a negative or non-finite utility; a member's base is not finite and positive (the reference's
+ * LP is then unbounded and the coalition skipped); a member's row of M is all zero or
+ * overflowed.  out_pivots = -2 and NaN: max_pivots exhausted (max_pivots = 0 gives -2 whenever a
+ * pivot is needed), or rounding left no column to enter or no positive sum.  The rest of the
+ * batch is unaffected.  Deterministic (no atomics): a (problem, coalition) gets the bits it
+ * gets alone.  No host sync, no allocation.
+ *
+ * Replaces: the HiGHS LPs of egalitarian_lottery (core.py:171-206) and of every coalition of
+ *   max_coalition_improvement (core.py:214-279), 2^n - 1 per call, three calls per (seed, rho)
+ *   of the reference's sweep (core.py:379-381).
+ */
+#define CS_MAXIMIN_MAX_PIVOTS 4096
+int cs_maximin_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ldu,
+                       int64_t ldp_problem, const double* base, const uint64_t* masks_host,
+                       const uint64_t* masks, int32_t C, int32_t max_pivots, double* out_alpha,
+                       double* out_q, double* out_lambda, int32_t* out_pivots, cs_stream_t stream);
+
+/*
  * cs_lottery_policy — the token-level policy a lottery over the m = B^L leaves of a B-ary tree
  * of depth L induces: pi(b | s) = mass(s + b) / mass(s), where mass(s) is the lottery's weight
  * on the contiguous block of leaves under prefix s (leaves in lexicographic order); a prefix of
