@@ -32,7 +32,7 @@ EXPORTED = (
     "cs_gemm_bf16_packed", "cs_gemm_pack", "cs_rope_place_splitk",
     "cs_add_rms_norm_splitk", "cs_prefix_attention_rows", "cs_rope_place_rows",
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
-    "cs_maximin_lottery",
+    "cs_maximin_lottery", "cs_policy_rollout",
 )
 
 
@@ -157,6 +157,8 @@ def load():
     L.cs_maximin_lottery.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i32, i32, vp, vp, vp,
                                      vp, vp]
     L.cs_maximin_lottery.restype = ctypes.c_int
+    L.cs_policy_rollout.argtypes = [vp, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]
+    L.cs_policy_rollout.restype = ctypes.c_int
     _lib = L
     return L
 

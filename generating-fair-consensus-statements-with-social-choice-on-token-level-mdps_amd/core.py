@@ -4,8 +4,9 @@ Same names, arguments and return types (NumPy in, NumPy out), but the per-step
 log-softmax + gather and the per-leaf folding run on the GPU through the C-ABI
 kernels (``ops.logsoftmax_gather`` -> ``ops.segment_reduce``), the point-mass
 welfare / selection through ``ops.welfare`` / ``ops.topk``, the Nash-welfare
-lottery and its induced policy through ``ops.nash_lottery`` / ``ops.lottery_policy``, and
-the maximin lottery and the coalition-improvement metric through ``ops.maximin_lottery``.
+lottery and its induced policy through ``ops.nash_lottery`` / ``ops.lottery_policy``, the
+maximin lottery and the coalition-improvement metric through ``ops.maximin_lottery``, and the
+rollout of the induced policy through ``ops.policy_rollout``.
 
 Reference (core.py):
   generate_params         49-56    (host RNG: parameters are inputs, not the hot path)
@@ -15,7 +16,11 @@ Reference (core.py):
   F_val                   108-113  (general lottery: host; point mass: point_mass_welfare)
   FW_nash_welfare         116-168  -> cs_nash_lottery (FW_nash_welfare_batch: a sweep per launch)
   build_prefix_index      287-294
-  induced_policy_rollout  297-332  -> cs_lottery_policy tables (induced_policy), host RNG draws
+  induced_policy_rollout  297-332  -> cs_lottery_policy tables (induced_policy), then
+                                      cs_policy_rollout: the reference's own PCG64 draws, made on
+                                      the GPU (induced_policy_rollout_batch: many lotteries per
+                                      launch)
+  main's sanity check     437-444  -> policy_equivalence_sweep: for every (seed, rho), not one
   utilitarian argmax      374-376  -> point_mass_select(U, "utilitarian")
   egalitarian_lottery     171-206  -> cs_maximin_lottery (all agents, base 1): one optimal vertex
   max_coalition_improvement 214-279 -> cs_maximin_lottery, every coalition's LP in one launch
@@ -319,27 +324,74 @@ def build_prefix_index(leaves):
     return index
 
 
+def _rollout_tv(pt, B, L, num_samples, states, what):
+    """(p_hat [P, m], tv [P]) of the lotteries pt [P, m] (device): one cs_lottery_policy and one
+    cs_policy_rollout launch, then the frequencies and distances one lottery at a time on 1-D
+    arrays, the reference's own expressions (core.py:330-331; a sum over an axis of a 2-D array
+    adds in another order)."""
+    res = ops.policy_rollout(ops.lottery_policy(pt, B, L, flat=True), B, L, states, num_samples)
+    if bool((res["status"] != 0).any()):
+        raise ops.CSError(f"{what}: a lottery's induced policy is not a policy (negative or "
+                          "non-finite mass; cs_policy_rollout status -1)")
+    counts = res["counts"].cpu().numpy()
+    ps = pt.cpu().numpy()
+    p_hat = np.empty(ps.shape, dtype=np.float64)
+    tv = np.empty(ps.shape[0], dtype=np.float64)
+    for k in range(ps.shape[0]):
+        p_hat[k] = counts[k] / counts[k].sum()
+        tv[k] = 0.5 * np.sum(np.abs(p_hat[k] - ps[k]))
+    return p_hat, tv
+
+
+def induced_policy_rollout_batch(ps, B, L, num_samples=200_000, seeds=7):
+    """induced_policy_rollout of the lotteries ps [P, m] in one cs_lottery_policy and one
+    cs_policy_rollout launch; ``seeds`` is one seed for all or one per lottery.  Every lottery
+    gets the draws of its own ``default_rng(seed)``, so each row is what the single call returns.
+    Returns (p_hat [P, m], tv [P])."""
+    ps = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64) for p in ps]))
+    if ps.ndim != 2:
+        raise ops.CSError("induced_policy_rollout_batch takes lotteries [P, m]")
+    if np.ndim(seeds) == 0:
+        seeds = [seeds] * ps.shape[0]
+    if len(seeds) != ps.shape[0]:
+        raise ops.CSError("induced_policy_rollout_batch takes one seed, or one per lottery")
+    states = np.stack([ops.pcg64_state(int(s)) for s in seeds])
+    return _rollout_tv(torch.as_tensor(ps, device=_device()), B, L, num_samples, states,
+                       "induced_policy_rollout")
+
+
 def induced_policy_rollout(p_star, leaves, B, L, num_samples=200_000, seed=7):
     """Sample leaves step by step from the policy p_star induces and compare their frequencies
     with p_star (core.py:297-332 contract): returns (p_hat, TV = 0.5 * |p_hat - p_star|_1).
 
     The step probabilities come from induced_policy's tables; the draws are the reference's
-    sequence of ``default_rng(seed).choice(B, p=probs)`` calls on the host."""
+    sequence of ``default_rng(seed).choice(B, p=probs)`` calls, made by cs_policy_rollout."""
     p_star = np.asarray(p_star, dtype=np.float64)
     leaves = [tuple(int(a) for a in leaf) for leaf in leaves]
     if leaves != enumerate_leaves(B, L):
         raise ops.CSError("induced_policy_rollout needs the leaves of enumerate_leaves(B, L)")
-    tables = induced_policy(p_star, B, L)
-    rng = np.random.default_rng(seed)
-    counts = np.zeros(len(leaves), dtype=np.int64)
-    for _ in range(num_samples):
-        s = 0                      # the prefix's index in base B
-        for t in range(L):
-            s = s * B + int(rng.choice(B, p=tables[t][s]))
-        counts[s] += 1
-    p_hat = counts / counts.sum()
-    tv = 0.5 * np.sum(np.abs(p_hat - p_star))
-    return p_hat, tv
+    p_hat, tv = induced_policy_rollout_batch(p_star[None], B, L, num_samples, seed)
+    return p_hat[0], tv[0]
+
+
+def policy_equivalence_sweep(B, L, d, n_agents, seeds, rho_grid, num_samples=200_000, seed=7,
+                             max_iters=1500, tol=1e-11):
+    """The reference's policy-lottery sanity check (core.py:437-444) for every (seed, rho) of the
+    sweep instead of one: the Nash-welfare lottery of each problem (one cs_nash_lottery launch),
+    the policies they induce (one cs_lottery_policy launch) and a rollout of ``num_samples``
+    leaves each with the draws of ``default_rng(seed)`` (one cs_policy_rollout launch).
+    Returns {"seeds", "rho", "tv" [len(seeds), len(rho_grid)]}."""
+    seeds = [int(s) for s in seeds]
+    rho_grid = np.asarray(rho_grid, dtype=np.float64).reshape(-1)
+    Us = []
+    for s in seeds:
+        v, w = generate_params(B, L, d, n_agents, seed=s)
+        Us.append(compute_utilities_fp64(v, w, rho_grid))
+    Us = torch.cat(Us).contiguous()                                              # [S * R, n, m]
+    p_nw = ops.nash_lottery(Us, max_iters=max_iters, tol=tol)["p"]
+    states = np.tile(ops.pcg64_state(seed), (Us.shape[0], 1))
+    _, tv = _rollout_tv(p_nw, B, L, num_samples, states, "policy_equivalence_sweep")
+    return {"seeds": np.array(seeds), "rho": rho_grid, "tv": tv.reshape(len(seeds), rho_grid.size)}
 
 
 _KIND = {"nash": "sumlog", "utilitarian": "sum", "egalitarian": "min"}

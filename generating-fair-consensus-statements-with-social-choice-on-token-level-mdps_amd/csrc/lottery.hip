@@ -1,6 +1,7 @@
 // lottery.hip — the Nash-welfare lottery over complete statements and the token policy it
-// induces (the reference's core.py:116-168 and 297-328), and the maximin lottery / coalition
-// improvement LPs (core.py:171-279), whole solves in one launch.
+// induces (the reference's core.py:116-168 and 297-328), the maximin lottery / coalition
+// improvement LPs (core.py:171-279), whole solves in one launch, and the rollout of a token
+// policy with numpy's own PCG64 draws (core.py:313-332).
 #include "cs_kernels.cuh"
 
 namespace {
@@ -623,6 +624,134 @@ void launch_maximin(hipStream_t st, int64_t grid, size_t lds, const double* U, i
                      out_q, out_lambda, out_pivots);
 }
 
+// ---------------------------------------------------------------------------
+// cs_policy_rollout: leaves sampled step by step from a token policy, with numpy's own draws
+// ---------------------------------------------------------------------------
+// Generator.choice(B, p=probs) is cdf = cumsum(probs); cdf /= cdf[-1]; u = random(); a = the
+// number of cdf entries <= u: one double of the PCG64 stream per draw.  Two kernels on the stream:
+//   rollout_cdf_kernel   one workgroup per problem, one thread per row of B probabilities: the
+//                        row is checked, summed left to right and divided by its last running
+//                        sum into cdf_work; the problem's status is written (0 / -1);
+//   rollout_walk_kernel  one workgroup per (problem, kRollPerGroup samples), each thread a
+//                        contiguous run of kRollPerThread samples: one O(log) jump of the LCG to
+//                        the run's first draw, then L sequential draws per sample.  The leaves
+//                        are counted in an int32 LDS histogram whose nonzero bins are added to
+//                        out_counts with integer atomics (the sums do not depend on the order).
+// A row's cdf is nondecreasing (running sums of entries >= 0, then a monotone division), so the
+// count of entries <= u is found by bisection.  A problem of status -1 is skipped by every
+// workgroup of the walk.
+constexpr int kRollBlock = 256;
+constexpr int kRollPerThread = 16;
+constexpr int kRollPerGroup = kRollBlock * kRollPerThread;   // 4096 samples
+constexpr double kRollSumTol = 0x1p-26;       // sqrt(DBL_EPSILON): numpy's check of sum(p)
+
+typedef unsigned __int128 u128;
+
+__host__ __device__ __forceinline__ u128 make_u128(uint64_t hi, uint64_t lo) {
+  return (static_cast<u128>(hi) << 64) | lo;
+}
+
+// PCG64's 128-bit LCG multiplier (0x2360ED051FC65DA4'4385DF649FCCF645)
+__device__ __forceinline__ u128 pcg_mult() {
+  return make_u128(0x2360ED051FC65DA4ull, 0x4385DF649FCCF645ull);
+}
+
+// the state after `delta` steps state <- state * mult + inc: square-and-multiply on (mult, inc)
+__device__ __forceinline__ u128 pcg_advance(u128 state, u128 inc, uint64_t delta) {
+  u128 acc_mult = 1, acc_plus = 0, cur_mult = pcg_mult(), cur_plus = inc;
+  while (delta > 0) {
+    if (delta & 1) {
+      acc_mult *= cur_mult;
+      acc_plus = acc_plus * cur_mult + cur_plus;
+    }
+    cur_plus = (cur_mult + 1) * cur_plus;
+    cur_mult *= cur_mult;
+    delta >>= 1;
+  }
+  return acc_mult * state + acc_plus;
+}
+
+// one step, then the XSL-RR output of the new state as numpy's double in [0, 1)
+__device__ __forceinline__ double pcg_next_double(u128& state, u128 inc) {
+  state = state * pcg_mult() + inc;
+  const uint64_t hi = static_cast<uint64_t>(state >> 64), lo = static_cast<uint64_t>(state);
+  const uint64_t x = hi ^ lo;
+  const unsigned rot = static_cast<unsigned>(hi >> 58);
+  const uint64_t out = (x >> rot) | (x << ((64u - rot) & 63u));
+  return static_cast<double>(out >> 11) * (1.0 / 9007199254740992.0);
+}
+
+__global__ __launch_bounds__(kRollBlock) void rollout_cdf_kernel(
+    const double* __restrict__ policy, int32_t B, int32_t rows, double* __restrict__ cdf,
+    int32_t* __restrict__ out_status) {
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * rows * B;
+  int bad = 0;
+  for (int32_t r = threadIdx.x; r < rows; r += kRollBlock) {
+    const double* row = policy + base + static_cast<int64_t>(r) * B;
+    double* out = cdf + base + static_cast<int64_t>(r) * B;
+    double acc = 0.0;
+    for (int32_t b = 0; b < B; ++b) {
+      const double v = row[b];
+      if (!(v >= 0.0) || v == INFINITY) bad = 1;
+      acc += v;
+      out[b] = acc;
+    }
+    if (!(fabs(acc - 1.0) <= kRollSumTol)) bad = 1;
+    for (int32_t b = 0; b < B; ++b) out[b] = out[b] / acc;
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) out_status[blockIdx.x] = bad ? -1 : 0;
+}
+
+__global__ __launch_bounds__(kRollBlock) void rollout_walk_kernel(
+    const double* __restrict__ cdf, int32_t B, int32_t L, int32_t m, int32_t rows,
+    const uint64_t* __restrict__ rng, int64_t first_sample, int64_t num_samples, int64_t chunks,
+    const int32_t* __restrict__ status, unsigned long long* __restrict__ out_counts,
+    int32_t* __restrict__ out_leaf) {
+  extern __shared__ __attribute__((aligned(16))) int32_t hist[];   // [m]
+  const int tid = threadIdx.x;
+  const int64_t prob = blockIdx.x / chunks;
+  const int64_t chunk = blockIdx.x % chunks;
+  if (status[prob] != 0) return;               // block-uniform
+  for (int32_t j = tid; j < m; j += kRollBlock) hist[j] = 0;
+  __syncthreads();
+
+  const int64_t first = chunk * kRollPerGroup + static_cast<int64_t>(tid) * kRollPerThread;
+  if (first < num_samples) {
+    const int64_t left = num_samples - first;
+    const int32_t n = left < kRollPerThread ? static_cast<int32_t>(left) : kRollPerThread;
+    const uint64_t* g = rng + prob * 4;
+    const u128 inc = make_u128(g[2], g[3]);
+    // sample i of the rollout owns the draws i * L .. i * L + L - 1 (< 2^62, checked on the host)
+    u128 state = pcg_advance(make_u128(g[0], g[1]), inc,
+                             static_cast<uint64_t>(first_sample + first) * static_cast<uint64_t>(L));
+    const double* pc = cdf + prob * rows * B;
+    for (int32_t i = 0; i < n; ++i) {
+      int32_t s = 0, row0 = 0, width = 1;      // row0: the level's first row, width = B^t rows
+      for (int32_t t = 0; t < L; ++t) {
+        const double u = pcg_next_double(state, inc);
+        const double* row = pc + static_cast<int64_t>(row0 + s) * B;
+        int32_t lo = 0, hi = B - 1;            // the last entry is 1.0 > u: a <= B - 1
+        while (lo < hi) {
+          const int32_t mid = (lo + hi) >> 1;
+          if (row[mid] <= u) lo = mid + 1;
+          else hi = mid;
+        }
+        s = s * B + lo;
+        row0 += width;
+        width *= B;
+      }
+      atomicAdd(&hist[s], 1);
+      if (out_leaf) out_leaf[prob * num_samples + first + i] = s;
+    }
+  }
+  __syncthreads();
+  for (int32_t j = tid; j < m; j += kRollBlock) {
+    const int32_t c = hist[j];
+    if (c) atomicAdd(out_counts + prob * m + j, static_cast<unsigned long long>(c));
+  }
+}
+
 // B^L if it is <= limit, else -1 (no overflow: stops at the first product past the limit)
 int64_t pow_limited(int32_t B, int32_t L, int64_t limit) {
   int64_t n = 1;
@@ -755,6 +884,50 @@ int cs_lottery_policy(const double* p, int32_t P, int32_t B, int32_t L, double* 
                      static_cast<hipStream_t>(stream), p, B, L, static_cast<int32_t>(m),
                      static_cast<int32_t>(total), out_policy);
   return check_launch("cs_lottery_policy");
+}
+
+int cs_policy_rollout(const double* policy, int32_t P, int32_t B, int32_t L, const uint64_t* rng,
+                      int64_t first_sample, int64_t num_samples, double* cdf_work,
+                      int64_t* out_counts, int32_t* out_leaf, int32_t* out_status,
+                      cs_stream_t stream) {
+  const std::string w = "cs_policy_rollout: ";
+  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
+  if (B < 1 || L < 1) return fail(CS_ERR_INVALID, w + "need B >= 1 and L >= 1");
+  if (L > kPolicyMaxL) return fail(CS_ERR_INVALID, w + "need L <= 64");
+  const int64_t m = pow_limited(B, L, kLotMaxM);
+  if (m < 0) return fail(CS_ERR_INVALID, w + "need B^L <= 16384");
+  if (first_sample < 0 || num_samples < 0)
+    return fail(CS_ERR_INVALID, w + "need first_sample >= 0 and num_samples >= 0");
+  const u128 draws = (static_cast<u128>(first_sample) + static_cast<u128>(num_samples)) * L;
+  if (draws >= (static_cast<u128>(1) << 62))
+    return fail(CS_ERR_INVALID, w + "need (first_sample + num_samples) * L < 2^62");
+  if (out_leaf && static_cast<u128>(P) * static_cast<u128>(num_samples) > 0x7fffffffu)
+    return fail(CS_ERR_INVALID, w + "out_leaf needs P * num_samples <= 2^31 - 1");
+  const int64_t chunks = (num_samples + kRollPerGroup - 1) / kRollPerGroup;
+  if (chunks > 0x7fffffffLL) return fail(CS_ERR_INVALID, w + "grid too large");
+  if (int rc = check_grid("cs_policy_rollout", static_cast<int64_t>(P) * chunks)) return rc;
+  if (P == 0 || num_samples == 0) return CS_OK;
+  if (!policy || !rng || !cdf_work || !out_counts || !out_status)
+    return fail(CS_ERR_INVALID, w + "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(policy) % 8 != 0 || reinterpret_cast<uintptr_t>(rng) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(cdf_work) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(out_counts) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(out_leaf) % 4 != 0 || reinterpret_cast<uintptr_t>(out_status) % 4 != 0)
+    return fail(CS_ERR_INVALID, w + "policy, rng, cdf_work and out_counts must be 8-byte aligned");
+  int64_t total = 0, n = 1;
+  for (int32_t t = 1; t <= L; ++t) {
+    n *= B;
+    total += n;
+  }
+  const int32_t rows = static_cast<int32_t>(total / B);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rollout_cdf_kernel, dim3(P), dim3(kRollBlock), 0, st, policy, B, rows, cdf_work,
+                     out_status);
+  hipLaunchKernelGGL(rollout_walk_kernel, dim3(static_cast<uint32_t>(P * chunks)), dim3(kRollBlock),
+                     static_cast<size_t>(m) * sizeof(int32_t), st, cdf_work, B, L,
+                     static_cast<int32_t>(m), rows, rng, first_sample, num_samples, chunks, out_status,
+                     reinterpret_cast<unsigned long long*>(out_counts), out_leaf);
+  return check_launch("cs_policy_rollout");
 }
 
 }  // extern "C"

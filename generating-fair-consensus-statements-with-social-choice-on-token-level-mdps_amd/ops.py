@@ -1178,12 +1178,13 @@ def maximin_lottery(U: torch.Tensor, base: Optional[torch.Tensor] = None, masks=
     return out if batched else {k: v[0] for k, v in out.items()}
 
 
-def lottery_policy(p: torch.Tensor, B: int, L: int):
+def lottery_policy(p: torch.Tensor, B: int, L: int, *, flat: bool = False):
     """The token policy a lottery over the B^L leaves (lexicographic order) induces
     (cs_lottery_policy): a list over the levels t = 0..L-1 of pi[t][s, b] = mass(s + b) / mass(s),
     [B^t, B] float64 (with a leading P for p [P, m]), views of one output; a prefix of mass <= 0
-    has the uniform 1/B.  Restates the masses and step probabilities of induced_policy_rollout
-    (core.py:303-325)."""
+    has the uniform 1/B.  flat=True returns that one output instead, [sum_t B^(t+1)] (or with a
+    leading P): the levels concatenated, what policy_rollout takes.  Restates the masses and
+    step probabilities of induced_policy_rollout (core.py:303-325)."""
     L_ = _lib.load()
     B, L = int(B), int(L)
     if p.dim() not in (1, 2) or p.dtype != torch.float64 or not p.is_contiguous():
@@ -1199,9 +1200,108 @@ def lottery_policy(p: torch.Tensor, B: int, L: int):
     out = torch.empty((P, sum(sizes)), dtype=torch.float64, device=p.device)
     rc = L_.cs_lottery_policy(p.data_ptr(), P, B, L, out.data_ptr(), _stream())
     _lib.check(rc, "cs_lottery_policy")
+    if flat:
+        return out if batched else out[0]
     levels, at = [], 0
     for n in sizes:
         blk = out[:, at:at + n].view(P, n // B, B)
         levels.append(blk if batched else blk[0])
         at += n
     return levels
+
+
+def pcg64_state(seed) -> np.ndarray:
+    """The stream of ``np.random.default_rng(seed)`` as policy_rollout takes it: uint64 [4], the
+    PCG64 state's high and low word, then the increment's high and low word."""
+    st = np.random.PCG64(seed).state["state"]
+    lo64 = (1 << 64) - 1
+    return np.array([st["state"] >> 64, st["state"] & lo64, st["inc"] >> 64, st["inc"] & lo64],
+                    dtype=np.uint64)
+
+
+def _rng_words(rng_state, P: int, batched: bool, device: torch.device) -> torch.Tensor:
+    """rng_state as the int64 bit patterns [P, 4] on the device."""
+    if isinstance(rng_state, torch.Tensor):
+        t = rng_state
+        if t.dtype == torch.uint64:
+            t = t.view(torch.int64)
+        if t.dtype != torch.int64:
+            raise CSError("rng_state must hold 64-bit words (uint64, or int64 bit patterns)")
+        _require_cuda(t)
+        if t.device != device:
+            raise CSError(f"tensors on different devices: {device} vs {t.device}")
+    else:
+        host = np.ascontiguousarray(rng_state)
+        if host.dtype != np.uint64 and host.dtype != np.int64:
+            raise CSError("rng_state must hold 64-bit words (uint64, or int64 bit patterns)")
+        t = torch.as_tensor(host.view(np.int64), device=device)
+    if tuple(t.shape) != ((P, 4) if batched else (4,)):
+        raise CSError("rng_state must be [4] (or [P, 4] for a batched policy): "
+                      "state high, state low, increment high, increment low")
+    return t.reshape(P, 4).contiguous()
+
+
+def policy_rollout(policy, B: int, L: int, rng_state, num_samples: int, first_sample: int = 0,
+                   counts: Optional[torch.Tensor] = None,
+                   with_leaves: bool = False) -> Dict[str, torch.Tensor]:
+    """Leaves sampled step by step from a token policy with numpy's own draws, counted per leaf
+    (cs_policy_rollout): sample i takes the draws i * L .. i * L + L - 1 of
+    ``default_rng(seed)``, each step is ``rng.choice(B, p=policy row)``.
+
+    policy: lottery_policy's result, either its list of levels or its flat=True tensor
+    [sum_t B^(t+1)] (or [P, ...]), float64; any token policy in that layout.
+    rng_state: pcg64_state(seed), [4] or [P, 4] (one stream per problem): a host uint64 array, or
+    a device tensor of uint64 / int64 bit patterns.
+    This call does the samples first_sample .. first_sample + num_samples - 1 and ADDS their
+    counts to ``counts`` (int64 [m] or [P, m]; None: fresh zeros), so a split rollout
+    accumulates to the counts of one call.
+    Returns {"counts", "status": int32 [..], "leaves": int32 [.., num_samples] with with_leaves}.
+    status -1: the problem's policy holds a negative or non-finite entry or a row that does not
+    sum to 1 within 2^-26 (where numpy's choice raises); its counts and leaves are untouched.
+    Restates the sampling loop of induced_policy_rollout (core.py:313-332)."""
+    L_ = _lib.load()
+    B, L = int(B), int(L)
+    num_samples, first_sample = int(num_samples), int(first_sample)
+    if isinstance(policy, (list, tuple)):
+        if not policy or any(not isinstance(t, torch.Tensor) for t in policy):
+            raise CSError("policy levels must be a non-empty list of tensors")
+        lead = policy[0].dim() == 3
+        policy = torch.cat([t.reshape(t.shape[0], -1) if lead else t.reshape(-1) for t in policy],
+                           dim=-1)
+    if policy.dim() not in (1, 2) or policy.dtype != torch.float64:
+        raise CSError("policy must be float64 [sum_t B^(t+1)] or [P, sum_t B^(t+1)] "
+                      "(or lottery_policy's list of levels)")
+    _require_cuda(policy, counts)
+    policy = policy.contiguous()
+    batched = policy.dim() == 2
+    P = policy.shape[0] if batched else 1
+    sizes = [B ** (t + 1) for t in range(L)] if 1 <= B and 1 <= L <= 64 else [0]
+    if sizes[-1] > 16384:
+        sizes = [0]          # the entry point rejects the shape; nothing that large is allocated
+    m = sizes[-1]
+    if m and policy.shape[-1] != sum(sizes):
+        raise CSError(f"policy has {policy.shape[-1]} entries per problem, "
+                      f"sum_t B^(t+1) is {sum(sizes)}")
+    dev = policy.device
+    rng = _rng_words(rng_state, P, batched, dev)
+    if counts is None:
+        counts = torch.zeros((P, m) if batched else (m,), dtype=torch.int64, device=dev)
+    elif (counts.dtype != torch.int64 or not counts.is_contiguous()
+          or tuple(counts.shape) != ((P, m) if batched else (m,))):
+        raise CSError("counts must be a contiguous int64 [m] (or [P, m]) tensor")
+    if with_leaves and P * num_samples >= 2 ** 31:
+        raise CSError("with_leaves needs P * num_samples <= 2^31 - 1")
+    work = torch.empty_like(policy)
+    status = torch.zeros(P, dtype=torch.int32, device=dev)
+    leaves = None
+    if with_leaves:      # -1: the leaves of a problem of status -1 stay untouched
+        leaves = torch.full((P, max(num_samples, 0)), -1, dtype=torch.int32, device=dev)
+    rc = L_.cs_policy_rollout(policy.data_ptr(), P, B, L, rng.data_ptr(), first_sample, num_samples,
+                              work.data_ptr(), counts.data_ptr(),
+                              leaves.data_ptr() if leaves is not None and leaves.numel() else None,
+                              status.data_ptr(), _stream())
+    _lib.check(rc, "cs_policy_rollout")
+    out = {"counts": counts, "status": status if batched else status[0]}
+    if with_leaves:
+        out["leaves"] = leaves if batched else leaves[0]
+    return out

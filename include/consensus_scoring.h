@@ -615,6 +615,54 @@ int cs_maximin_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t
 int cs_lottery_policy(const double* p, int32_t P, int32_t B, int32_t L, double* out_policy,
                       cs_stream_t stream);
 
+/*
+ * cs_policy_rollout — leaves of the B-ary tree of depth L sampled step by step from a token
+ * policy, for P problems at once, with exactly the draws of the reference's
+ * ``rng = default_rng(seed)`` and ``rng.choice(B, p=probs)`` per step, and a count per leaf.
+ *
+ * The draw rule (numpy's Generator.choice with a scalar result): per row of B probabilities
+ * cdf = the running sum in action order (fp64, sequential), every entry then divided by the
+ * last; u = the next double of the stream; a = the number of cdf entries <= u (searchsorted,
+ * side "right").  A zero-probability action has a cdf entry equal to its predecessor's and is
+ * never chosen, action 0 at u = 0.0 included; the last entry is exactly 1.0 > u, so a <= B - 1.
+ * A walk starts at s = 0 and takes s <- s * B + a for L levels; s is then the leaf's index.
+ * The stream is PCG64: state <- state * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128),
+ * then x = (high word ^ low word) rotated right by state >> 122, u = (x >> 11) * 2^-53.
+ * One draw is one step, so a thread reaches its own samples with an O(log) jump-ahead and no
+ * uniforms are made or uploaded by the host.
+ *
+ * policy [P][sum_{t=1..L} B^t]: per-level tables in cs_lottery_policy's output layout (any
+ * token policy on the tree, not only a lottery-induced one).
+ * rng [P][4]: per problem the PCG64 state's high and low word and the increment's high and low
+ * word, the two 128-bit integers of np.random.PCG64(seed).state["state"].
+ * Sample i of the whole rollout takes the draws i * L .. i * L + L - 1 of its problem's stream;
+ * this call does the samples first_sample .. first_sample + num_samples - 1, so a rollout split
+ * over several calls gives the counts of one call.
+ * cdf_work: scratch of policy's size (the cdf tables).
+ * out_counts [P][B^L] int64 is ADDED TO: the caller zeroes it, split calls accumulate.
+ * out_leaf: nullable, [P][num_samples] int32, the leaf each sample of this call reached.
+ * out_status [P]: 0 done; -1 the problem's policy holds a negative or non-finite entry, or a row
+ * whose sum is further than 2^-26 (1.49e-8, numpy's sqrt(eps) check, where the reference would
+ * raise) from 1: its counts and leaves are left untouched, the rest of the batch is unaffected.
+ *
+ * B >= 1, 1 <= L <= 64, B^L <= 16384, P >= 0, first_sample >= 0, num_samples >= 0,
+ * (first_sample + num_samples) * L < 2^62, P * num_samples <= 2^31 - 1 when out_leaf is given;
+ * pointers non-NULL and 8-byte aligned (out_leaf, out_status: 4).  P = 0 or num_samples = 0
+ * returns CS_OK, launches nothing and writes nothing.
+ * Two kernels on the stream: the cdf tables and statuses (one workgroup per problem), then the
+ * walk (one workgroup per problem and 4096 samples, 16 consecutive samples per thread).  Counts
+ * go through an int32 histogram in LDS (B^L * 4 bytes) and reach out_counts by integer atomic
+ * adds: the sums do not depend on the order, so the result is deterministic and a problem gets
+ * the counts it gets alone.  No host sync, no allocation.
+ *
+ * Replaces: the sampling loop of induced_policy_rollout (core.py:313-332), num_samples * L
+ *   rng.choice calls on the host, run by the reference for one lottery (core.py:437-444).
+ */
+int cs_policy_rollout(const double* policy, int32_t P, int32_t B, int32_t L, const uint64_t* rng,
+                      int64_t first_sample, int64_t num_samples, double* cdf_work,
+                      int64_t* out_counts, int32_t* out_leaf, int32_t* out_status,
+                      cs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
