@@ -20,6 +20,8 @@ CS_F32, CS_BF16, CS_F16 = 0, 1, 2
 WELFARE_MIN, WELFARE_SUM, WELFARE_SUMLOG, WELFARE_MAX = 0, 1, 2, 3
 NONFINITE_SKIP, NONFINITE_REPLACE = 0, 1
 MAXIMIN_MAX_PIVOTS = 4096     # CS_MAXIMIN_MAX_PIVOTS
+SCHULZE_RANKINGS, SCHULZE_SCORES, SCHULZE_DEFEATS, SCHULZE_STRENGTHS = 0, 1, 2, 3
+SCHULZE_MAX_C, SCHULZE_MAX_R, SCHULZE_TILE = 128, 65536, 32   # csrc/schulze.hip
 
 EXPORTED = (
     "cs_version", "cs_last_error", "cs_workspace_size", "cs_logsoftmax_gather",
@@ -32,7 +34,7 @@ EXPORTED = (
     "cs_gemm_bf16_packed", "cs_gemm_pack", "cs_rope_place_splitk",
     "cs_add_rms_norm_splitk", "cs_prefix_attention_rows", "cs_rope_place_rows",
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
-    "cs_maximin_lottery", "cs_policy_rollout",
+    "cs_maximin_lottery", "cs_policy_rollout", "cs_schulze",
 )
 
 
@@ -159,6 +161,8 @@ def load():
     L.cs_maximin_lottery.restype = ctypes.c_int
     L.cs_policy_rollout.argtypes = [vp, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]
     L.cs_policy_rollout.restype = ctypes.c_int
+    L.cs_schulze.argtypes = [vp, ctypes.c_int, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cs_schulze.restype = ctypes.c_int
     _lib = L
     return L
 

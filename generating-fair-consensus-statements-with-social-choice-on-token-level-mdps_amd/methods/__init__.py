@@ -3,9 +3,12 @@
 GENERATOR_MAP / get_method_generator(method_name, method_config, generation_model)
 -> generator_class(model_identifier, config).  The three scoring methods named by
 the hot path and MCTS (the same agent-scoring primitive)
-run on the local engine; the other reference methods (habermas_machine, zero_shot,
+run on the local engine; the other reference generators (habermas_machine, zero_shot,
 predefined) make no agent x candidate scoring calls, are outside this build's
-scope and are not registered.
+scope and are not registered.  The Habermas Machine's aggregation rule,
+Schulze rank aggregation, does run here (methods/habermas_machine.py, cs_schulze) as
+drop-ins for the reference's functions and as Best-of-N's ``selection: "schulze"``;
+only its LLM-prompted generator (prompts, parsing, critique rounds) is left out.
 """
 from .base import BaseGenerator
 from .beam_search import BeamSearchGenerator

@@ -13,12 +13,17 @@ Reference flow (best_of_n.py:53-207), same config keys and outputs:
 Under torchrun (one process per GPU, default process group over several ranks) the agents
 are sharded (parallel.method_shard): each rank scores its agents x all candidates and the
 welfare is combined with an all-reduce(MIN); every rank returns the same statement.
+
+Config key ``selection`` (not in the reference): "egalitarian" (the default) is the flow above;
+"schulze" returns the Schulze winner of the agents' rankings by utility instead, the Habermas
+Machine's aggregation rule (cs_schulze on the gathered [A, N] utilities, one launch).
 """
 from __future__ import annotations
 
 import logging
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from .. import ops, parallel, runtime, utils
@@ -57,6 +62,7 @@ class BestOfNGenerator(BaseGenerator):
         self.last_candidates: List[str] = []
         self.last_agent_rewards: Dict[str, List[float]] = {}
         self.last_welfare: List[float] = []
+        self.last_social_ranking: List[int] = []
 
     @runtime.serialized()
     def generate_statement(self, issue: str, agent_opinions: dict) -> str:
@@ -65,6 +71,9 @@ class BestOfNGenerator(BaseGenerator):
         max_tokens = cfg.get("max_tokens", 50)
         seed = cfg.get("seed")
         temperature = cfg.get("temperature", 1.0)
+        selection = cfg.get("selection", "egalitarian")
+        if selection not in ("egalitarian", "schulze"):
+            raise ValueError(f"Unknown selection: {selection!r} (egalitarian or schulze)")
         engine, tok = runtime.get_engine(self.model_identifier)
 
         ref_user = BON["ref_user"].format(issue=issue, opinions_text=opinions_text(agent_opinions))
@@ -83,11 +92,37 @@ class BestOfNGenerator(BaseGenerator):
         W = parallel.combine_welfare(U, "min", shard, nonfinite="replace",
                                      nan_val=self.DEFAULT_REWARD, posinf_val=self.REWARD_CLIP_MAX,
                                      neginf_val=self.REWARD_CLIP_MIN)
+        if selection == "schulze":
+            b = self._schulze_winner(U, shard, seed)
+            self.last_welfare = W.double().cpu().tolist()
+            logger.info("Selected Schulze winner index: %d (Score: %.4f)", b, self.last_welfare[b])
+            return cands[b]
         best, _ = ops.topk(W, 1)
         b = int(best.item())
         self.last_welfare = W.double().cpu().tolist()
         logger.info("Selected best candidate index: %d (Score: %.4f)", b, self.last_welfare[b])
         return cands[b]
+
+    def _schulze_winner(self, U: torch.Tensor, shard, seed) -> int:
+        """The Habermas Machine's selection rule on the agents' utilities: every agent ranks the
+        candidates by its own utility and the rankings are aggregated by Schulze (cs_schulze,
+        scores mode), ties broken by the ballot default_rng(seed).permutation(N) as
+        _aggregate_schulze draws it.  Non-finite utilities are replaced as the welfare path
+        replaces them.  Records last_social_ranking (untied, 0 = the returned candidate)."""
+        allU = parallel.gather_agents(U.to(torch.float32), shard)
+        S = torch.nan_to_num(allU, nan=self.DEFAULT_REWARD, posinf=self.REWARD_CLIP_MAX,
+                             neginf=self.REWARD_CLIP_MIN).contiguous()
+        n = S.shape[1]
+        ballot = np.random.default_rng(seed).permutation(n).astype(np.int32)
+        ballot = parallel.same_on_all_ranks(ballot, shard)   # seed=None draws differ per rank
+        res = ops.schulze(S[None], kind="scores",
+                          ballot=torch.as_tensor(ballot[None], device=S.device),
+                          with_defeats=False, with_strengths=False)
+        if int(res["status"].item()) != 0:
+            raise ops.CSError(f"cs_schulze could not aggregate {tuple(S.shape)} utilities "
+                              f"(status {int(res['status'].item())})")
+        self.last_social_ranking = res["untied"][0].cpu().tolist()
+        return int(res["winner"].item())
 
     def score_candidates(self, issue: str, agent_opinions: dict, cands: List[str],
                          shard: Optional[parallel.AgentShard] = None) -> torch.Tensor:

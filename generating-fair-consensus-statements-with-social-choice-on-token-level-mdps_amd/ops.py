@@ -1305,3 +1305,72 @@ def policy_rollout(policy, B: int, L: int, rng_state, num_samples: int, first_sa
     if with_leaves:
         out["leaves"] = leaves if batched else leaves[0]
     return out
+
+
+SCHULZE_KINDS = {"rankings": _lib.SCHULZE_RANKINGS, "scores": _lib.SCHULZE_SCORES,
+                 "defeats": _lib.SCHULZE_DEFEATS, "strengths": _lib.SCHULZE_STRENGTHS}
+
+
+def schulze(x: torch.Tensor, kind: str = "rankings", valid: Optional[torch.Tensor] = None,
+            ballot: Optional[torch.Tensor] = None, *, with_defeats: bool = True,
+            with_strengths: bool = True) -> Dict[str, torch.Tensor]:
+    """Schulze rank aggregation of a batch of elections in one launch (cs_schulze), one workgroup
+    per election.
+
+    x by ``kind``: "rankings" int32 [E, R, C] (lower is better, ties allowed), "scores" float32
+    [E, R, C] (higher is better; a NaN prefers nothing), "defeats" int32 [E, C, C] (skips the
+    pairwise count), "strengths" int32 [E, C, C] (skips the path strengths too).  C <= 128,
+    R <= 65536.  valid [E, R] (bool or uint8; rankings and scores only): the voters that count.
+    ballot int32 [E, C]: the tie-breaking ballot (any values, repeats allowed).
+    Returns {"defeats" [E, C, C] (rankings / scores, with_defeats), "strengths" [E, C, C] (all
+    but kind "strengths", with_strengths), "ranking" [E, C] the tied social ranking, "untied"
+    [E, C] (ballot given), "winner" [E] the lowest index of rank 0 (of "untied" when there is
+    one), "status" [E]}, all int32.  status -1: a counted rank outside [0, C - 1] or a nonzero
+    diagonal (the reference's ValueErrors), -2: valid leaves no voter; that election's other
+    outputs are -1, the rest of the batch is unaffected.
+    Restates _schulze_compute_pairwise_defeats, _schulze_compute_strongest_path_strengths,
+    _schulze_rank_candidates and _hm_untie_ranking_with_ballot
+    (src/methods/habermas_machine.py:992-1160)."""
+    L = _lib.load()
+    if kind not in SCHULZE_KINDS:
+        raise CSError(f"unknown kind {kind!r} (one of {sorted(SCHULZE_KINDS)})")
+    k = SCHULZE_KINDS[kind]
+    voters = k <= _lib.SCHULZE_SCORES
+    want = torch.float32 if k == _lib.SCHULZE_SCORES else torch.int32
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != want:
+        raise CSError(f"x must be a {want} tensor [E, R, C] (rankings, scores) or [E, C, C] "
+                      f"(defeats, strengths) for kind {kind!r}")
+    _require_cuda(x, valid, ballot)
+    if not voters and x.shape[1] != x.shape[2]:
+        raise CSError(f"{kind} must be square per election, got {tuple(x.shape)}")
+    if not voters and valid is not None:
+        raise CSError("valid applies to rankings and scores only")
+    x = x.contiguous()
+    E, R, C = x.shape
+    dev = x.device
+    if valid is not None:
+        if valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (E, R):
+            raise CSError("valid must be a bool or uint8 [E, R] tensor")
+        valid = valid.to(torch.uint8).contiguous()
+    if ballot is not None:
+        if ballot.dtype != torch.int32 or tuple(ballot.shape) != (E, C):
+            raise CSError("ballot must be an int32 [E, C] tensor")
+        ballot = ballot.contiguous()
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+
+    defeats = new(E, C, C) if voters and with_defeats else None
+    strengths = new(E, C, C) if k != _lib.SCHULZE_STRENGTHS and with_strengths else None
+    ranking, winner, status = new(E, C), new(E), new(E)
+    untied = new(E, C) if ballot is not None else None
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731
+    rc = L.cs_schulze(x.data_ptr(), k, E, R, C, ptr(valid), ptr(ballot), ptr(defeats),
+                      ptr(strengths), ranking.data_ptr(), ptr(untied), winner.data_ptr(),
+                      status.data_ptr(), _stream())
+    _lib.check(rc, "cs_schulze")
+    out = {"ranking": ranking, "winner": winner, "status": status}
+    for name, t in (("defeats", defeats), ("strengths", strengths), ("untied", untied)):
+        if t is not None:
+            out[name] = t
+    return out

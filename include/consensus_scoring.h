@@ -663,6 +663,62 @@ int cs_policy_rollout(const double* policy, int32_t P, int32_t B, int32_t L, con
                       int64_t* out_counts, int32_t* out_leaf, int32_t* out_status,
                       cs_stream_t stream);
 
+/*
+ * cs_schulze — Schulze rank aggregation of E independent elections in one launch, one
+ * workgroup per election: R voters' rankings of C candidates become pairwise defeats,
+ * strongest-path strengths, a (possibly tied) social ranking, a ranking untied by a ballot, and
+ * a winner.  Integer arithmetic throughout: the result is the reference's bit for bit.
+ *
+ * in_kind selects the stage at which the data enters:
+ *   CS_SCHULZE_RANKINGS   in = int32 [E][R][C] ranks, lower is better, ties allowed
+ *   CS_SCHULZE_SCORES     in = float [E][R][C] scores, higher is better
+ *   CS_SCHULZE_DEFEATS    in = int32 [E][C][C] pairwise defeats (skips stage 1)
+ *   CS_SCHULZE_STRENGTHS  in = int32 [E][C][C] path strengths (skips stages 1 and 2)
+ * R, valid and out_defeats are ignored where stage 1 is skipped, out_strengths where stage 2 is.
+ *
+ * Stage 1: d[i][j] = the number of counted voters r with rank[r][i] < rank[r][j] (scores:
+ *   score[r][i] > score[r][j]; a NaN compares false both ways, infinities as usual); diagonal 0.
+ *   valid [E][R] (nullable = all; bytes, any alignment): voter r counts iff valid[r] != 0.
+ * Stage 2: p[i][j] = d[i][j] > d[j][i] ? d[i][j] : 0, diagonal 0; then for every pivot k in
+ *   ascending order and all (j, l), j != k, l != k, j != l:
+ *   p[j][l] = max(p[j][l], min(p[j][k], p[k][l])).  A pivot reads only row k and column k and
+ *   writes neither, so its updates run in parallel with one barrier per pivot and give the
+ *   sequential loop's result.  The entries may be any integers (kind DEFEATS).
+ * Stage 3: count[i] = #{j : p[i][j] >= p[j][i]} (j = i included); out_ranking[i] = the number
+ *   of distinct counts greater than count[i] (np.unique(-count, return_inverse=True)).
+ * Tie-break (ballot [E][C] given; any int32 values, repeats allowed): nb[i] = the number of
+ *   distinct ballot values below ballot[i], key[i] = out_ranking[i] * C + nb[i],
+ *   out_untied[i] = the number of distinct keys below key[i].
+ * out_winner[e] = the lowest index of rank 0 in the untied ranking when a ballot is given, else
+ *   in out_ranking.
+ * out_status[e]: 0 solved; -1 malformed (a counted voter's rank outside [0, C - 1], or a nonzero
+ *   diagonal in a DEFEATS / STRENGTHS input: the reference's ValueErrors); -2 valid leaves no
+ *   voter.  Every other output of such an election is filled with -1; the rest of the batch is
+ *   unaffected.
+ *
+ * 1 <= C <= 128, 1 <= R <= 65536, E >= 0 (E = 0 returns CS_OK and launches nothing).  in,
+ * out_ranking and out_status are required, the other pointers nullable; out_untied needs
+ * ballot; all but valid 4-byte aligned.
+ * LDS: the C x C matrix with row stride C | 1, one tile of 32 voters and five vectors of C,
+ * 84,992 bytes at C = 128; the voters stream through the tile, so R does not grow it.  One wave
+ * per workgroup up to C = 16, four above.  Deterministic (no atomics), no host sync, no
+ * allocation.
+ *
+ * Replaces: _schulze_compute_pairwise_defeats, _schulze_compute_strongest_path_strengths,
+ *   _schulze_rank_candidates, _hm_untie_ranking_with_ballot and the winner's selection
+ *   (src/methods/habermas_machine.py:992-1024, 1048-1160), three nested Python loops per stage.
+ */
+enum cs_schulze_kind {
+  CS_SCHULZE_RANKINGS = 0,
+  CS_SCHULZE_SCORES = 1,
+  CS_SCHULZE_DEFEATS = 2,
+  CS_SCHULZE_STRENGTHS = 3
+};
+int cs_schulze(const void* in, int in_kind, int32_t E, int32_t R, int32_t C, const uint8_t* valid,
+               const int32_t* ballot, int32_t* out_defeats, int32_t* out_strengths,
+               int32_t* out_ranking, int32_t* out_untied, int32_t* out_winner, int32_t* out_status,
+               cs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
