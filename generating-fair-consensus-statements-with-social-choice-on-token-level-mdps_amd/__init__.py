@@ -19,6 +19,6 @@ def __getattr__(name):
     import importlib
 
     if name in ("ops", "core", "engine", "model", "tokenizer", "utils", "methods", "evaluation",
-                "parallel", "scoring", "build"):
+                "parallel", "scoring", "build", "runtime"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -35,6 +35,7 @@ EXPORTED = (
     "cs_add_rms_norm_splitk", "cs_prefix_attention_rows", "cs_rope_place_rows",
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
     "cs_maximin_lottery", "cs_policy_rollout", "cs_schulze",
+    "cs_sample_step_workspace_size", "cs_sample_step",
 )
 
 
@@ -163,6 +164,11 @@ def load():
     L.cs_policy_rollout.restype = ctypes.c_int
     L.cs_schulze.argtypes = [vp, ctypes.c_int, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cs_schulze.restype = ctypes.c_int
+    L.cs_sample_step_workspace_size.argtypes = [i64, i64]
+    L.cs_sample_step_workspace_size.restype = ctypes.c_size_t
+    L.cs_sample_step.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, vp, vp, i32, f32, vp,
+                                 i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.cs_sample_step.restype = ctypes.c_int
     _lib = L
     return L
 

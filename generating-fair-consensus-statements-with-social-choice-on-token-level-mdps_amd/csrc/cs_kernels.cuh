@@ -57,7 +57,8 @@ inline int check_launch(const char* what) {
 }
 
 // Argument checks shared by the entry points that stream whole logits rows
-// (cs_logsoftmax_gather, cs_vocab_topk, cs_vocab_sample, cs_beam_step, cs_beam_decode_step).
+// (cs_logsoftmax_gather, cs_vocab_topk, cs_vocab_sample, cs_sample_step, cs_beam_step,
+// cs_beam_decode_step).
 // `fn` is the entry point's name; each returns CS_OK or the status after fail().
 inline int check_logits(const char* fn, int dtype, int64_t vocab, int64_t ld) {
   if (dtype != CS_F32 && dtype != CS_BF16 && dtype != CS_F16)

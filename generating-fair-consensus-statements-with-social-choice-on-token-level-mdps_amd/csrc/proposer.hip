@@ -151,22 +151,49 @@ __device__ __forceinline__ void draw_merge(float& s, int32_t& i, float s2, int32
   }
 }
 
-template <int DT, bool CAP>
+// What cs_sample_step adds to the streaming stage (SampleMode > kSamplePlain): the row's one
+// seed is derived on the device from (base seed, *step), a finished stream's workgroups leave
+// before they touch its row, and (kSampleStepBias) the listed tokens take bias_value in fp32
+// before the soft-cap, looked up in an LDS bitmap over the workgroup's slice of the vocabulary.
+enum SampleMode { kSamplePlain = 0, kSampleStep = 1, kSampleStepBias = 2 };
+struct StepIn {
+  const int32_t* step;
+  const int32_t* done;
+  const int32_t* bias_ids;
+  int32_t n_bias;
+  float bias_value;
+};
+constexpr unsigned long long kSeedMul = 1000003ull;   // runtime.draw_seed
+constexpr int64_t kMaxBiasSlice = 1 << 19;            // bitmap <= 64 KB of LDS
+
+template <int DT, bool CAP, int MODE>
 __global__ __launch_bounds__(256) void vocab_sample_kernel(
     const char* __restrict__ logits, int64_t vocab, int64_t ld_bytes, int32_t nsplit,
     int64_t split_len, float inv_temp, float cap, float inv_cap,
     const unsigned long long* __restrict__ seeds, int32_t n_draw, float2* __restrict__ lse_part,
-    DrawBest* __restrict__ draw_part) {
+    DrawBest* __restrict__ draw_part, StepIn in) {
+  extern __shared__ uint32_t sm_bias[];   // kSampleStepBias: one bit per token of [v0, v1)
   __shared__ float sm_m[4], sm_s[4];
   __shared__ float sm_bs[4][kMaxDraws];
   __shared__ int32_t sm_bi[4][kMaxDraws];
   const int tid = threadIdx.x;
   const int64_t bid = blockIdx.x;
   const int64_t row = bid / nsplit;
+  if (MODE != kSamplePlain && in.done[row] != 0) return;   // block-uniform, before any barrier
   const int32_t split = static_cast<int32_t>(bid - row * nsplit);
   const char* rp = logits + row * ld_bytes;
   const int64_t v0 = static_cast<int64_t>(split) * split_len;
   const int64_t v1 = min(vocab, v0 + split_len);
+  if (MODE == kSampleStepBias) {
+    const int nw = static_cast<int>((v1 - v0 + 31) >> 5);
+    for (int w = tid; w < nw; w += 256) sm_bias[w] = 0u;
+    __syncthreads();
+    for (int j = tid; j < in.n_bias; j += 256) {
+      const int64_t id = in.bias_ids[j];
+      if (id >= v0 && id < v1) atomicOr(&sm_bias[(id - v0) >> 5], 1u << ((id - v0) & 31));
+    }
+    __syncthreads();
+  }
   unsigned long long sd[kMaxDraws];
   float bs[kMaxDraws];
   int32_t bi[kMaxDraws];
@@ -176,10 +203,16 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
     bs[d] = -INFINITY;
     bi[d] = 0x7fffffff;
   }
+  if (MODE != kSamplePlain)   // n_draw = 1
+    sd[0] = sd[0] * kSeedMul + static_cast<unsigned long long>(static_cast<int64_t>(*in.step));
   float m = -INFINITY, s = 0.0f;
   bool saw_nan = false;
   for (int64_t v = v0 + tid; v < v1; v += 256) {
     float x = load_any<DT>(rp, v);
+    if (MODE == kSampleStepBias) {
+      const int64_t o = v - v0;
+      if ((sm_bias[o >> 5] >> (o & 31)) & 1u) x += in.bias_value;
+    }
     if (CAP) x = softcap_fn(x, cap, inv_cap);
     const float y = x * inv_temp;
     saw_nan |= y != y;
@@ -273,6 +306,78 @@ __global__ __launch_bounds__(64) void vocab_sample_merge_kernel(
   }
 }
 
+// cs_sample_step's second stage, one wave per stream: the split merge of
+// vocab_sample_merge_kernel (same order, so the id and the log-prob are its bits), then the
+// stream's state update and the next step's input token.  Lane 0 of every workgroup adds
+// (1 << 32 | still alive) to the workspace's one counter word; the last arrival has the
+// number of unfinished streams in the low half, writes it and leaves the word at zero.
+template <int DT, bool CAP>
+__global__ __launch_bounds__(64) void sample_step_merge_kernel(
+    const char* __restrict__ logits, int64_t ld_bytes, int32_t nsplit, float inv_temp, float cap,
+    float inv_cap, const float2* __restrict__ lse_part, const DrawBest* __restrict__ draw_part,
+    StepIn in, const int32_t* __restrict__ stop_ids, int32_t n_stop, int32_t max_tokens,
+    int32_t pad_id, int32_t* __restrict__ done, int32_t* __restrict__ out_len,
+    int32_t* __restrict__ out_tokens, float* __restrict__ out_lp,
+    long long* __restrict__ next_tok, int32_t* __restrict__ n_alive,
+    unsigned long long* __restrict__ arrivals) {
+  const int64_t row = blockIdx.x;
+  const int lane = threadIdx.x;
+  int32_t next = pad_id;
+  uint32_t alive = 0u;
+  if (done[row] == 0) {   // block-uniform
+    float m = -INFINITY, s = 0.0f;
+    for (int j = lane; j < nsplit; j += 64) {
+      const float2 p = lse_part[row * nsplit + j];
+      lse_merge(m, s, p.x, p.y);
+    }
+    wave_lse_reduce(m, s);
+    const float lse = m + logf(s);
+    float b = -INFINITY;
+    int32_t i = 0x7fffffff;
+    for (int j = 0; j < nsplit; ++j) {  // split order: ties keep the lower token id
+      const DrawBest p = draw_part[row * nsplit + j];
+      draw_merge(b, i, p.s, p.idx);
+    }
+    bool hit = false;
+    for (int j = lane; j < in.n_bias; j += 64) hit |= in.bias_ids[j] == i;
+    const bool biased = __ballot(hit) != 0ull;
+    if (lane == 0) {
+      bool stop = i == 0x7fffffff;   // no drawable logit: the stream ends
+      for (int j = 0; j < n_stop; ++j) stop |= stop_ids[j] == i;
+      const int32_t len = out_len[row];
+      // a length outside [0, max_tokens) has no slot to append to: the stream ends as well
+      if (stop || len < 0 || len >= max_tokens) {
+        done[row] = 1;
+      } else {
+        const int64_t at = row * max_tokens + len;
+        out_tokens[at] = i;
+        if (out_lp) {
+          float x = load_any<DT>(logits + row * ld_bytes, i);
+          if (biased) x += in.bias_value;
+          if (CAP) x = softcap_fn(x, cap, inv_cap);
+          out_lp[at] = x * inv_temp - lse;
+        }
+        out_len[row] = len + 1;
+        if (len + 1 == max_tokens) {
+          done[row] = 1;
+        } else {
+          next = i;
+          alive = 1u;
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    next_tok[row] = next;
+    const unsigned long long old = __hip_atomic_fetch_add(
+        arrivals, (1ull << 32) | alive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((old >> 32) == static_cast<unsigned long long>(gridDim.x) - 1ull) {
+      n_alive[0] = static_cast<int32_t>((old & 0xffffffffull) + alive);
+      __hip_atomic_store(arrivals, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 int32_t topk_nchunk(int64_t vocab) {
   return static_cast<int32_t>((vocab + kTopkChunk - 1) / kTopkChunk);
 }
@@ -359,14 +464,80 @@ int cs_vocab_sample(const void* logits, int dtype, int64_t rows, int64_t vocab, 
   dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
     constexpr int DT = decltype(dt)::value;
     constexpr bool CAP = decltype(cap)::value;
-    hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows * plan.nsplit)),
-                       dim3(256), 0, st, lg, vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t,
-                       softcap, inv_cap, sd, n_draw, lse_part, draw_part);
+    hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP, kSamplePlain>),
+                       dim3(static_cast<uint32_t>(rows * plan.nsplit)), dim3(256), 0, st, lg, vocab,
+                       ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap, sd, n_draw,
+                       lse_part, draw_part, StepIn{});
     hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows)), dim3(64),
                        0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part, draw_part,
                        n_draw, out_ids, out_lp);
   });
   return check_launch("cs_vocab_sample");
+}
+
+// workspace: the arrival word, then the partials of cs_vocab_sample with one draw
+size_t cs_sample_step_workspace_size(int64_t S, int64_t vocab) {
+  if (S <= 0 || vocab <= 0) return 0;
+  return sizeof(unsigned long long) + cs_vocab_sample_workspace_size(S, vocab, 1);
+}
+
+int cs_sample_step(const void* logits, int dtype, int64_t S, int64_t vocab, int64_t ld,
+                   float temperature, float softcap, const uint64_t* base_seeds,
+                   const int32_t* step, const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                   const int32_t* stop_ids, int32_t n_stop, int32_t max_tokens, int32_t pad_id,
+                   int32_t* done, int32_t* out_len, int32_t* out_tokens, float* out_lp,
+                   int64_t* next_tok, int32_t* n_alive, void* workspace, size_t workspace_bytes,
+                   cs_stream_t stream) {
+  const char* fn = "cs_sample_step";
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (S < 0) return fail(CS_ERR_INVALID, std::string(fn) + ": need S >= 0");
+  if (n_bias < 0 || n_bias > 1024 || n_stop < 0 || n_stop > 16)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 <= n_bias <= 1024 and 0 <= n_stop <= 16");
+  if (max_tokens < 1) return fail(CS_ERR_INVALID, std::string(fn) + ": need max_tokens >= 1");
+  if (pad_id < 0 || pad_id >= vocab)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": pad_id outside [0, vocab)");
+  if (!(temperature > 0.0f) || std::isinf(temperature))
+    return fail(CS_ERR_INVALID, std::string(fn) + ": temperature must be finite and > 0");
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  if (S == 0) return CS_OK;
+  if (!logits || !base_seeds || !step || !done || !out_len || !out_tokens || !next_tok || !n_alive ||
+      (n_bias > 0 && !bias_ids) || (n_stop > 0 && !stop_ids))
+    return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
+  const SplitPlan plan = plan_split(S, vocab, CS_F32);   // cs_vocab_sample's, for its bits
+  if (int rc = check_grid(fn, S * plan.nsplit)) return rc;
+  if (n_bias > 0 && plan.split_len > kMaxBiasSlice)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": a biased row slice exceeds 2^19 tokens");
+  if (int rc = check_workspace(fn, workspace, workspace_bytes, cs_sample_step_workspace_size(S, vocab)))
+    return rc;
+  auto* arrivals = static_cast<unsigned long long*>(workspace);
+  auto* lse_part = reinterpret_cast<float2*>(arrivals + 1);
+  auto* draw_part = reinterpret_cast<DrawBest*>(lse_part + S * plan.nsplit);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t ld_bytes = ld * elt_size(dtype);
+  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
+  const float inv_t = 1.0f / temperature;
+  const char* lg = static_cast<const char*>(logits);
+  const auto* sd = reinterpret_cast<const unsigned long long*>(base_seeds);
+  const StepIn in{step, done, bias_ids, n_bias, bias_value};
+  const dim3 grid(static_cast<uint32_t>(S * plan.nsplit));
+  const size_t bitmap = static_cast<size_t>((plan.split_len + 31) / 32) * sizeof(uint32_t);
+  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
+    constexpr int DT = decltype(dt)::value;
+    constexpr bool CAP = decltype(cap)::value;
+    if (n_bias > 0)
+      hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP, kSampleStepBias>), grid, dim3(256), bitmap, st,
+                         lg, vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap,
+                         sd, 1, lse_part, draw_part, in);
+    else
+      hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP, kSampleStep>), grid, dim3(256), 0, st, lg,
+                         vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap, sd,
+                         1, lse_part, draw_part, in);
+    hipLaunchKernelGGL((sample_step_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(S)), dim3(64),
+                       0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part, draw_part,
+                       in, stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
+                       reinterpret_cast<long long*>(next_tok), n_alive, arrivals);
+  });
+  return check_launch("cs_sample_step");
 }
 
 }  // extern "C"

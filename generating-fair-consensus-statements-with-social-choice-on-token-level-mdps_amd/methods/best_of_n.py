@@ -17,6 +17,10 @@ welfare is combined with an all-reduce(MIN); every rank returns the same stateme
 Config key ``selection`` (not in the reference): "egalitarian" (the default) is the flow above;
 "schulze" returns the Schulze winner of the agents' rankings by utility instead, the Habermas
 Machine's aggregation rule (cs_schulze on the gathered [A, N] utilities, one launch).
+Config key ``generation`` (not in the reference): "host" (the default) draws the candidates
+through runtime.generate; "device" draws them through runtime.generate_streams (graph-replayed
+decode steps ending in cs_sample_step, no host round trip per token; bf16 engines).  Everything
+after the candidates is shared.
 """
 from __future__ import annotations
 
@@ -59,6 +63,9 @@ class BestOfNGenerator(BaseGenerator):
         super().__init__(model_identifier, config)
         logger.setLevel(getattr(logging, str(config.get("log_level", "INFO")).upper(), logging.INFO))
         self.api_delay = config.get("api_delay", 0.1)  # accepted for compatibility; no remote calls
+        self.generation = config.get("generation", "host")
+        if self.generation not in ("host", "device"):
+            raise ValueError(f"Unknown generation: {self.generation!r} (host or device)")
         self.last_candidates: List[str] = []
         self.last_agent_rewards: Dict[str, List[float]] = {}
         self.last_welfare: List[float] = []
@@ -79,7 +86,11 @@ class BestOfNGenerator(BaseGenerator):
         ref_user = BON["ref_user"].format(issue=issue, opinions_text=opinions_text(agent_opinions))
         ref_ids, _ = tok.render_chat(BON["ref_system"], ref_user)
         seeds = [seed + i if seed is not None else None for i in range(n)]
-        outs = runtime.generate(engine, tok, ref_ids, seeds, max_tokens, float(temperature))
+        if self.generation == "device":
+            outs = runtime.generate_streams(engine, tok, [ref_ids], seeds, max_tokens,
+                                            float(temperature))[0]
+        else:
+            outs = runtime.generate(engine, tok, ref_ids, seeds, max_tokens, float(temperature))
         cands = [c for c in (clean_generated_text(tok.decode(o)) for o in outs) if c]
         shard = parallel.method_shard(len(agent_opinions), cfg)
         cands = parallel.same_on_all_ranks(cands, shard)   # seed=None draws differ per rank

@@ -449,6 +449,69 @@ def vocab_sample(logits: torch.Tensor, seeds: torch.Tensor, *, temperature: floa
     return ids, lp
 
 
+_sample_ws: dict = {}
+
+
+def _state_ptr(t: Optional[torch.Tensor], name: str, dtype: torch.dtype, shape: tuple):
+    """Pointer of one of sample_step's state tensors (None stays NULL for the library to judge)."""
+    if t is None:
+        return None
+    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        raise CSError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}")
+    return t.data_ptr()
+
+
+def sample_step(logits: torch.Tensor, base_seeds: torch.Tensor, step: torch.Tensor,
+                done: torch.Tensor, out_len: torch.Tensor, out_tokens: torch.Tensor,
+                next_tok: torch.Tensor, n_alive: torch.Tensor, *, pad_id: int,
+                temperature: float = 1.0, softcap: float = 0.0,
+                bias_ids: Optional[torch.Tensor] = None, bias_value: float = -1e6,
+                stop_ids: Optional[torch.Tensor] = None, out_lp: Optional[torch.Tensor] = None,
+                max_tokens: Optional[int] = None, vocab: Optional[int] = None,
+                workspace: Optional[Workspace] = None) -> None:
+    """One generation step of S streams in place (cs_sample_step): the draw of
+    ``vocab_sample`` with seed draw_seed(base_seeds[s], step[0]) on the biased row, the stop
+    test, the append to out_tokens [S, max_tokens] / out_lp / out_len, the next input token
+    (next_tok [S] int64: the id, or pad_id once the stream is done) and n_alive [1].
+
+    Every argument that changes between steps (step [1] int32, done / out_len [S] int32) lives
+    on the device and nothing is allocated here, so the call replays inside a captured graph.
+    bias_ids / stop_ids: int32 device tensors (None or empty: none).  The workspace is a
+    Workspace(zeroed=True) used by this op alone."""
+    L = _lib.load()
+    S, ld, vocab = _logits_args(logits, vocab)
+    _require_cuda(logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
+                  bias_ids, stop_ids, out_lp)
+    if max_tokens is None:
+        if out_tokens is None or out_tokens.dim() != 2:
+            raise CSError("out_tokens must be [S, max_tokens] int32")
+        max_tokens = out_tokens.shape[1]
+    max_tokens = int(max_tokens)
+    lists = []
+    for name, t in (("bias_ids", bias_ids), ("stop_ids", stop_ids)):
+        n = 0 if t is None else t.numel()
+        if n and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise CSError(f"{name} must be a contiguous 1-D int32 tensor")
+        lists += [t.data_ptr() if n else None, n]
+    dev = logits.device
+    workspace, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _sample_ws, int(L.cs_sample_step_workspace_size(S, vocab)), dev, "sample_step")
+    rc = L.cs_sample_step(
+        logits.data_ptr(), _DTYPE[logits.dtype], S, vocab, ld, float(temperature), float(softcap),
+        _state_ptr(base_seeds, "base_seeds", torch.int64, (S,)),
+        _state_ptr(step, "step", torch.int32, (1,)), lists[0], lists[1], float(bias_value),
+        lists[2], lists[3], max_tokens, int(pad_id),
+        _state_ptr(done, "done", torch.int32, (S,)),
+        _state_ptr(out_len, "out_len", torch.int32, (S,)),
+        _state_ptr(out_tokens, "out_tokens", torch.int32, (S, max_tokens)),
+        _state_ptr(out_lp, "out_lp", torch.float32, (S, max_tokens)),
+        _state_ptr(next_tok, "next_tok", torch.int64, (S,)),
+        _state_ptr(n_alive, "n_alive", torch.int32, (1,)), ws_ptr, ws_bytes, _stream())
+    if rc != 0:
+        workspace.reset()
+    _lib.check(rc, "cs_sample_step")
+
+
 class AttnPlan:
     """A cs_prefix_attention work plan on the device (entries, counts) and the split
     partials' workspace it needs; built once per (prefix-length bounds, shape) and reused by

@@ -330,3 +330,102 @@ def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int
         st.advance(parent, toks)
         alive = nxt
     return out
+
+
+def _seed_lists(seeds, n_prompts: int) -> List[List[int]]:
+    """generate_streams' ``seeds``: one list for every prompt, or one list per prompt."""
+    seeds = list(seeds)
+    if seeds and all(isinstance(s, (list, tuple)) for s in seeds):
+        if len(seeds) != n_prompts:
+            raise ValueError(f"{len(seeds)} seed lists for {n_prompts} prompts")
+        per = [list(s) for s in seeds]
+    else:
+        per = [list(seeds) for _ in range(n_prompts)]
+    return [[fresh_seed() if s is None else int(s) for s in row] for row in per]
+
+
+@torch.no_grad()
+def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
+                     prefixes: Sequence[Sequence[int]], seeds, max_tokens: int,
+                     temperature: float = 1.0, bias_ids: Sequence[int] = (),
+                     bias_value: float = -1e6, stop_ids: Optional[Sequence[int]] = None,
+                     poll_every: int = 8, return_logprobs: bool = False):
+    """Sample continuations of many prompts at once with the loop closed on the device:
+    result[p][i] = the tokens of prompt p under seeds[p][i] (``seeds``: one list used for
+    every prompt, or one list per prompt, of any lengths), drawn as ``generate`` draws
+    them (token t with draw_seed(seed, t), a stop token ends the stream and is not
+    included).  With ``return_logprobs`` the result is (tokens, log-probs), same nesting.
+
+    One DecodeState holds every stream; a step is one graph replay whose last launches are
+    the LM head and cs_sample_step, which appends the draw and writes the next step's input
+    token on the device.  The host reads one word (the number of unfinished streams) every
+    ``poll_every`` steps and downloads the tokens once at the end.  bf16 engines only: the
+    stream decode is the bf16 path, and another dtype raises instead of changing numerics."""
+    from .engine import DecodeState
+    P = len(prefixes)
+    per = _seed_lists(seeds, P)
+    B = max((len(r) for r in per), default=0)
+    max_tokens = int(max_tokens)
+    toks: List[List[List[int]]] = [[[] for _ in r] for r in per]
+    lps: List[List[List[float]]] = [[[] for _ in r] for r in per]
+    if P == 0 or B == 0 or max_tokens <= 0:
+        return (toks, lps) if return_logprobs else toks
+    m = engine.model
+    if m.dtype != torch.bfloat16:
+        raise ops.CSError(f"generate_streams needs a bf16 engine (this one is {m.dtype}): the "
+                          "stream decode is the bf16 path; runtime.generate serves every dtype")
+    if not m.fused_ok():
+        raise ops.CSError(f"generate_streams: the stream kernels do not serve this model's heads "
+                          f"(head_dim {m.cfg.head_dim}); runtime.generate does")
+    stop = list(tok.eos_ids if stop_ids is None else stop_ids)
+    dev = engine.device
+    S = P * B
+    with device_lock(dev):
+        sp = engine.prefill_streams([list(p) for p in prefixes])
+        ds = DecodeState(engine, sp, n_prefix=P, n_beams=B, max_steps=max(1, max_tokens - 1),
+                         use_graphs=True)
+        try:
+            base = [to_i64(r[b]) if b < len(r) else 0 for r in per for b in range(B)]
+            done0 = [0 if b < len(r) else 1 for r in per for b in range(B)]
+            base_t = torch.tensor(base, dtype=torch.int64, device=dev)
+            done = torch.tensor(done0, dtype=torch.int32, device=dev)
+            out_len = torch.zeros(S, dtype=torch.int32, device=dev)
+            out_tok = torch.zeros(S, max_tokens, dtype=torch.int32, device=dev)
+            out_lp = torch.zeros(S, max_tokens, dtype=torch.float32, device=dev) \
+                if return_logprobs else None
+            n_alive = torch.zeros(1, dtype=torch.int32, device=dev)
+            alive_h = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+            bias_t = torch.tensor(list(bias_ids), dtype=torch.int32, device=dev) if bias_ids else None
+            stop_t = torch.tensor(stop, dtype=torch.int32, device=dev) if stop else None
+            pad_id = int(tok.eos_ids[0]) if getattr(tok, "eos_ids", None) else 0
+            ws = ops.Workspace(zeroed=True)
+
+            def post():
+                logits = m.lm_head(ds.hidden)                      # [S, V]
+                ops.sample_step(logits, base_t, ds.hist_base, done, out_len, out_tok, ds.tok,
+                                n_alive, pad_id=pad_id, temperature=float(temperature),
+                                softcap=engine.softcap, bias_ids=bias_t,
+                                bias_value=float(bias_value), stop_ids=stop_t, out_lp=out_lp,
+                                workspace=ws)
+
+            post()                                 # token 0: every stream = its prompt
+            every = max(1, int(poll_every))
+            for a in range(max_tokens - 1):
+                if a % every == 0:
+                    alive_h.copy_(n_alive, non_blocking=True)
+                    torch.cuda.current_stream().synchronize()
+                    if int(alive_h[0]) == 0:
+                        break
+                ds.advance_device(post=post)
+            lens_h = out_len.cpu().tolist()        # one download (synchronises)
+            tok_h = out_tok.cpu().numpy()
+            lp_h = out_lp.cpu().numpy() if return_logprobs else None
+        finally:
+            ds.release()
+    for p, r in enumerate(per):
+        for b in range(len(r)):
+            s = p * B + b
+            toks[p][b] = tok_h[s, :lens_h[s]].tolist()
+            if return_logprobs:
+                lps[p][b] = lp_h[s, :lens_h[s]].tolist()
+    return (toks, lps) if return_logprobs else toks

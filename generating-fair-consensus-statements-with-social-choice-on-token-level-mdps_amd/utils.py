@@ -592,3 +592,59 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
     except Exception as e:
         logger.error("generate_text failed: %s", e)
         return f"[ERROR: {type(e).__name__}]"
+
+
+def generate_texts(model, user_prompts, system_prompts=None, n_per_prompt=1, max_tokens=4096,
+                   temperature=1, terminators=(), seeds=None, bias_against_tokens=None,
+                   bias_value=-1000000, use_chat_completions=True) -> List[List[str]]:
+    """The batch form of generate_text: result[p][i] = completion i of prompt p, every prompt
+    and sample decoded together on the device (runtime.generate_streams; bf16 engines).
+
+    system_prompts: None, one string for every prompt, or one per prompt.  seeds: None
+    (fresh seeds), one list of n_per_prompt seeds used for every prompt, or one list per
+    prompt.  Rendering, the terminator cut and the '[ERROR: ...]' contract are generate_text's:
+    a failure puts the error string in every slot."""
+    users = list(user_prompts)
+    P = len(users)
+    n = int(n_per_prompt)
+    if seeds is not None:
+        sl = list(seeds)
+        if sl and all(isinstance(s, (list, tuple)) for s in sl):
+            shape = [len(s) for s in sl] + [n] * max(0, P - len(sl))
+        else:
+            shape = [len(sl)] * P
+    else:
+        shape = [n] * P
+    try:
+        engine, tok = runtime.get_engine(model)
+        if system_prompts is None or isinstance(system_prompts, str):
+            systems = [system_prompts] * P
+        else:
+            systems = list(system_prompts)
+            if len(systems) != P:
+                raise ValueError(f"{len(systems)} system prompts for {P} user prompts")
+        idss = []
+        for sysp, user in zip(systems, users):
+            if use_chat_completions:
+                ids, _ = tok.render_chat(sysp or None, user)
+            else:
+                ids = tok.render_raw(f"{sysp}\n\n{user}" if sysp else f"{user}")
+            idss.append(ids)
+        bias = runtime.bias_token_ids(tok, bias_against_tokens)
+        outs = runtime.generate_streams(engine, tok, idss, [None] * n if seeds is None else seeds,
+                                        max_tokens, float(temperature), bias_ids=bias,
+                                        bias_value=float(bias_value))
+        texts = []
+        for row in outs:
+            texts.append([])
+            for out in row:
+                text = tok.decode(out)
+                for term in terminators or ():
+                    cut = text.find(term)
+                    if cut != -1:
+                        text = text[:cut]
+                texts[-1].append(text)
+        return texts
+    except Exception as e:
+        logger.error("generate_texts failed: %s", e)
+        return [[f"[ERROR: {type(e).__name__}]"] * k for k in shape[:P]]

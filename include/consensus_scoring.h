@@ -267,6 +267,47 @@ int cs_vocab_sample(const void* logits, int dtype, int64_t rows, int64_t vocab, 
                     cs_stream_t stream);
 
 /*
+ * cs_sample_step — one generation step of S independent streams after the LM head: the
+ * seeded draw, the stop test, the append and the next step's input token.  Everything that
+ * changes between steps is read from device memory, so a captured graph replays the call
+ * with no new argument and no memset between replays.
+ *
+ * With t = *step (device, int32), for stream s:
+ *   done[s] != 0: next_tok[s] = pad_id, nothing else of the stream is written and its logits
+ *     row is not read.
+ *   otherwise: id, lp = the one draw of cs_vocab_sample with seed
+ *     (base_seeds[s] * 1000003 + t) mod 2^64 (runtime.draw_seed) on the row
+ *     x[v] = float(logits[s][v]) + (v listed in bias_ids ? bias_value : 0), the bias added in
+ *     fp32 before the soft-cap, once per token however often it is listed, ids outside
+ *     [0, vocab) ignored.  Bit for bit cs_vocab_sample(rows = S, n_draw = 1) on that fp32 row.
+ *     id == -1 (no drawable logit) or id in stop_ids: done[s] = 1, nothing appended.
+ *     else: out_tokens[s][out_len[s]] = id, out_lp[s][out_len[s]] = lp (out_lp nullable),
+ *       out_len[s] += 1, and done[s] = 1 once out_len[s] == max_tokens.  (A stream handed
+ *       over with out_len outside [0, max_tokens) is ended without an append.)
+ *     next_tok[s] (int64, the layout of DecodeState.tok) = id while the stream is unfinished
+ *       after the step, else pad_id.
+ *   n_alive[0] = number of streams with done == 0 after the call.
+ * Limits: n_bias <= 1024, n_stop <= 16, max_tokens >= 1, 0 <= pad_id < vocab, and with
+ * n_bias > 0 at most 2^19 tokens per row slice (vocab / the split count of the plan).
+ * S = 0 is CS_OK and writes nothing.
+ *
+ * WORKSPACE: cs_sample_step_workspace_size() bytes, zero-filled before the first call, used
+ * by one stream at a time, left zeroed where it counts (one arrival word) by every call.
+ *
+ * Replaces: the remote completion loop behind generate_text (src/utils.py:69-118) for many
+ *   prompts at once, as the Best-of-N candidates (src/methods/best_of_n.py:104-118) and the
+ *   Habermas Machine's per-agent prompts need it.
+ */
+size_t cs_sample_step_workspace_size(int64_t S, int64_t vocab);
+int cs_sample_step(const void* logits, int dtype, int64_t S, int64_t vocab, int64_t ld,
+                   float temperature, float softcap, const uint64_t* base_seeds,
+                   const int32_t* step, const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                   const int32_t* stop_ids, int32_t n_stop, int32_t max_tokens, int32_t pad_id,
+                   int32_t* done, int32_t* out_len, int32_t* out_tokens, float* out_lp,
+                   int64_t* next_tok, int32_t* n_alive, void* workspace, size_t workspace_bytes,
+                   cs_stream_t stream);
+
+/*
  * cs_prefix_attention — cascade attention of many candidate streams over SHARED
  * per-agent prefix K/V (bf16 in / bf16 out, fp32 online softmax, bf16 MFMA).
  *
