@@ -19,6 +19,6 @@ def __getattr__(name):
     import importlib
 
     if name in ("ops", "core", "engine", "model", "tokenizer", "utils", "methods", "evaluation",
-                "parallel", "scoring", "build", "runtime"):
+                "parallel", "scoring", "build", "runtime", "encoder", "checkpoint"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

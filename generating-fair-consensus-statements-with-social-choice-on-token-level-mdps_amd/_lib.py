@@ -36,6 +36,8 @@ EXPORTED = (
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
     "cs_maximin_lottery", "cs_policy_rollout", "cs_schulze",
     "cs_sample_step_workspace_size", "cs_sample_step",
+    "cs_embed_layer_norm", "cs_add_layer_norm", "cs_gelu", "cs_encoder_attention",
+    "cs_cosine_welfare",
 )
 
 
@@ -169,6 +171,18 @@ def load():
     L.cs_sample_step.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, vp, vp, i32, f32, vp,
                                  i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     L.cs_sample_step.restype = ctypes.c_int
+    L.cs_embed_layer_norm.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, i32, vp, vp, vp, i64, f32,
+                                      vp, i64, vp, vp]
+    L.cs_embed_layer_norm.restype = ctypes.c_int
+    L.cs_add_layer_norm.argtypes = [vp, i64, vp, i64, vp, vp, i64, i64, f32, vp, i64, vp]
+    L.cs_add_layer_norm.restype = ctypes.c_int
+    L.cs_gelu.argtypes = [vp, i64, i64, i64, vp, i64, vp]
+    L.cs_gelu.restype = ctypes.c_int
+    L.cs_encoder_attention.argtypes = [vp, i64, vp, i32, i64, i32, i32, i32, f32, vp, vp]
+    L.cs_encoder_attention.restype = ctypes.c_int
+    L.cs_cosine_welfare.argtypes = [vp, i64, vp, i64, vp, vp, i32, i32, i64, ctypes.c_double, vp,
+                                    vp, vp]
+    L.cs_cosine_welfare.restype = ctypes.c_int
     _lib = L
     return L
 

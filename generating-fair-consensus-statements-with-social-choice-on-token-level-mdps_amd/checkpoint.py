@@ -154,3 +154,47 @@ def save_checkpoint(model: Model, path: str, tokenizer_dir: Optional[str] = None
             src = os.path.join(tokenizer_dir, n)
             if os.path.exists(src):
                 shutil.copy(src, os.path.join(path, n))
+
+
+# --- text encoders (BertModel checkpoints: BAAI/bge-*-en-v1.5) -----------------------------
+def encoder_config_from_hf(conf: dict, name: str = "checkpoint"):
+    from .encoder import EncoderConfig
+
+    if conf.get("model_type") != "bert":
+        raise ValueError(f"unsupported encoder model_type {conf.get('model_type')!r} ('bert')")
+    if conf.get("hidden_act", "gelu") != "gelu" or \
+            conf.get("position_embedding_type", "absolute") != "absolute":
+        raise ValueError("the encoder kernels serve erf-GELU and learned absolute positions only")
+    d, H = conf["hidden_size"], conf["num_attention_heads"]
+    return EncoderConfig(name=name, vocab=conf["vocab_size"], d_model=d,
+                         n_layers=conf["num_hidden_layers"], n_heads=H, d_ff=conf["intermediate_size"],
+                         n_pos=conf["max_position_embeddings"], n_types=conf.get("type_vocab_size", 2),
+                         ln_eps=float(conf.get("layer_norm_eps", 1e-12)), head_dim=d // H)
+
+
+def load_encoder(path: str, device=None):
+    """(TextEncoder, WordPieceTokenizer) of a local Hugging Face ``BertModel`` directory:
+    config.json, *.safetensors under Hugging Face's parameter names (with or without the
+    ``bert.`` prefix) and tokenizer.json.  Weights are cast to bf16 (the encoder's only dtype)
+    and q | k | v are fused per layer."""
+    from safetensors import safe_open
+
+    from .encoder import TextEncoder, fuse_hf_weights
+    from .tokenizer import WordPieceTokenizer
+
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = encoder_config_from_hf(json.load(f), name=os.path.basename(os.path.normpath(path)))
+    dev = torch.device(device) if device is not None else \
+        torch.device("cuda", torch.cuda.current_device())
+    files = sorted(glob.glob(os.path.join(path, "*.safetensors")))
+    if not files:
+        raise FileNotFoundError(f"no *.safetensors under {path}")
+    sd: Dict[str, torch.Tensor] = {}
+    for fn in files:
+        with safe_open(fn, framework="pt", device="cpu") as sf:
+            for k in sf.keys():
+                if "embeddings." in k or "encoder.layer." in k:
+                    sd[k] = sf.get_tensor(k).to(device=dev, dtype=torch.bfloat16)
+    enc = TextEncoder(cfg, dev, weights=fuse_hf_weights(sd, cfg))
+    tok = WordPieceTokenizer(path, max_len=cfg.n_pos, vocab_size=cfg.vocab)
+    return enc, tok

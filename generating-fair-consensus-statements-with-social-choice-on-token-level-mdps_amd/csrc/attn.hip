@@ -25,6 +25,8 @@
 //                        layout) and V (transposed layout) into the per-stream buffers;
 //                        positions come from device memory (prefix length + history base),
 //                        so a captured decode step replays with no host input but ids.
+//   encoder_attn_kernel  bidirectional attention of the text encoder over a ragged batch, from
+//                        the same pieces (described where it stands, at the end of the file).
 //
 // Layouts (all bf16, D = head_dim in {64, 128, 256}):
 //   q       [n_tok, H, D], token tok = s*T + t of stream s = grp*n_str + b
@@ -1414,6 +1416,193 @@ int cs_rope_place_splitk_rows(const float* part, int32_t splits, const float* in
   return rope_place_splitk_impl("cs_rope_place_splitk_rows", part, splits, inv_freq, prefix_len,
                                 group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
                                 k_hist, v_hist, ld_hist, 1, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// encoder_attn_kernel -- bidirectional softmax attention of the text encoder (encoder.hip)
+// over a ragged batch: text t is tokens cu[t] .. cu[t + 1] - 1 of the fused projection
+// qkv [n_tok][3 H 64] (q | k | v, each [H][64], K AND V row-major as in the rows route), and
+// a token sees every key of its own text and none of another's.  One workgroup per (text,
+// head, 64-query tile) walks the text's 32-key blocks, each staged through LDS once for the
+// workgroup's four 16-query tiles, double-buffered as CS_ATTEND_STAGED does it.
+//
+// From the shared pieces: LdsTile (the padded K / V^T buffers), mine_staged, attend_staged
+// (so attend_block: the arithmetic, mask and lazy rescale are the decoders'), combine_waves
+// (a text of <= 32 queries gives its tile's key blocks to 2 or 4 waves) and store_out.  Its
+// own: the TileRows it fills (tile_rows derives a row from the group / stream / GQA layout,
+// a ragged text has none), the Q load (load_q takes q [n_tok][H][D]; here Q sits inside the
+// fused row at another pitch) and the staging (fetch_chunks / stage_chunks copy a block that
+// is contiguous, whole, and already V^T; here the rows are 3 H 64 apart, the keys past the
+// text's end are another text's and must not be read -- they are staged as zeros, so the
+// output cannot depend on a neighbour, NaN included -- and V is transposed on its way in).
+namespace {
+
+struct EncAttnParams {
+  const __bf16* qkv;
+  int64_t ldqkv;
+  const int32_t* cu;
+  __bf16* out;
+  int64_t n_tok;
+  int32_t n_text, H, n_qt, max_len;   // n_qt: 64-query tiles of the longest text
+  float scale;
+};
+
+constexpr int kEncD = 64;
+
+// this thread's 16-byte chunk of key block kb: key tid / 8, d 8 (tid % 8) .. + 7 of K and of V
+// (zeros past the text's end)
+__device__ __forceinline__ void enc_fetch(const __bf16* kbase, int64_t ld, int kb, int len, u32x4& rk,
+                                          u32x4& rv, int H) {
+  const int key = kb + (static_cast<int>(threadIdx.x) >> 3);
+  if (key < len) {
+    const __bf16* p = kbase + key * ld + 8 * (threadIdx.x & 7);
+    rk = *reinterpret_cast<const u32x4*>(p);
+    rv = *reinterpret_cast<const u32x4*>(p + H * kEncD);
+  } else {
+    rk = u32x4{0u, 0u, 0u, 0u};
+    rv = u32x4{0u, 0u, 0u, 0u};
+  }
+}
+
+// ... into block j's buffer: the K chunk as it is, the V chunk's 8 d as 8 V^T rows
+__device__ __forceinline__ void enc_stage(__bf16* buf, int j, const u32x4& rk, const u32x4& rv) {
+  using LT = LdsTile<kEncD>;
+  __bf16* kd = buf + (j & 1) * LT::ELEMS;
+  uint16_t* vd = reinterpret_cast<uint16_t*>(kd + LT::KELEMS);
+  const int key = static_cast<int>(threadIdx.x) >> 3, ch = threadIdx.x & 7;
+  *reinterpret_cast<u32x4*>(kd + key * LT::KROW + 8 * ch) = rk;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t wv = rv[e >> 1];
+    vd[(8 * ch + e) * LT::VROW + key] = static_cast<uint16_t>((e & 1) ? (wv >> 16) : (wv & 0xffffu));
+  }
+}
+
+__global__ __launch_bounds__(kAttnThreads, 2)
+void encoder_attn_kernel(EncAttnParams e) {
+  constexpr int D = kEncD;
+  using LT = LdsTile<D>;
+  __shared__ __attribute__((aligned(16))) char lds[LT::kBytes];
+  const int bid = blockIdx.x;
+  const int qtile = bid % e.n_qt;
+  const int h = (bid / e.n_qt) % e.H;
+  const int t = bid / (e.n_qt * e.H);
+  const int64_t t0 = e.cu[t];
+  const int64_t t1 = e.cu[t + 1];
+  // a malformed cu_seqlens reads and writes nothing (workgroup-uniform, before any barrier)
+  if (t0 < 0 || t1 <= t0 || t1 > e.n_tok || t1 - t0 > e.max_len) return;
+  const int len = static_cast<int>(t1 - t0);
+  const int q0 = qtile * kGroupRows;
+  if (q0 >= len) return;
+
+  AttnParams a = {};
+  a.out = e.out;
+  a.H = e.H;
+  a.scale = e.scale;
+  a.softcap = 0.0f;
+  a.inv_softcap = 0.0f;
+
+  TileRows tr = {};
+  tr.M = len;
+  tr.r0 = q0;
+  tr.nrows = min(kGroupRows, len - q0);
+  tr.n_qt = (tr.nrows + 15) >> 4;
+  tr.kw = tr.n_qt == 1 ? 4 : (tr.n_qt == 2 ? 2 : 1);
+  tr.w = threadIdx.x >> 6;
+  tr.lane = threadIdx.x & 63;
+  tr.qt = tr.w % tr.n_qt;
+  tr.ks = tr.w / tr.n_qt;
+  tr.active = tr.ks < tr.kw;
+  tr.col = tr.lane & 15;
+  tr.h4 = tr.lane >> 4;
+  const int row = q0 + tr.qt * 16 + tr.col;
+  tr.vrow = tr.active && row < len;
+  tr.tok = t0 + (row < len ? row : len - 1);
+  tr.head = h;
+  tr.kmin_pos = INT32_MIN;
+
+  bf16x8 qf[D / 32];
+  {
+    const __bf16* qrow = e.qkv + tr.tok * e.ldqkv + h * D + 8 * tr.h4;
+#pragma unroll
+    for (int ds = 0; ds < D / 32; ++ds) {
+      if (tr.vrow) {
+        qf[ds] = *reinterpret_cast<const bf16x8*>(qrow + ds * 32);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) qf[ds][i] = static_cast<__bf16>(0.0f);
+      }
+    }
+  }
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.0f;
+
+  const int lim = tr.vrow ? len : 0;
+  auto ref = [&](int j) {
+    BlockRef r;
+    r.k = nullptr;
+    r.vt = nullptr;
+    r.mask = BlockMask{j * kKeyBlock, lim, 0};
+    return r;
+  };
+  const __bf16* kbase = e.qkv + t0 * e.ldqkv + (e.H + h) * D;
+  const int n = (len + kKeyBlock - 1) / kKeyBlock;
+  __bf16* buf = reinterpret_cast<__bf16*>(lds);
+  u32x4 rk, rv;
+  enc_fetch(kbase, e.ldqkv, 0, len, rk, rv, e.H);
+  enc_stage(buf, 0, rk, rv);
+  __syncthreads();
+  for (int j = 0; j < n; ++j) {
+    const bool more = j + 1 < n;
+    if (more) enc_fetch(kbase, e.ldqkv, (j + 1) * kKeyBlock, len, rk, rv, e.H);
+    if (mine_staged(tr, j)) attend_staged<D>(a, tr, buf, j, ref, qf, o, m, l);
+    if (more) enc_stage(buf, j + 1, rk, rv);
+    __syncthreads();
+  }
+  combine_waves<D>(tr, lds, o, m, l);
+  if (tr.vrow && tr.ks == 0) store_out<D>(a, tr, o, l);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cs_encoder_attention(const void* qkv, int64_t ld_qkv, const int32_t* cu_seqlens, int32_t n_text,
+                         int64_t n_tok, int32_t max_seqlen, int32_t H, int32_t D, float scale,
+                         void* out, cs_stream_t stream) {
+  const std::string nm = "cs_encoder_attention";
+  if (n_text < 0 || n_tok < 0 || max_seqlen < 0) return fail(CS_ERR_INVALID, nm + ": negative size");
+  if (D != kEncD) return fail(CS_ERR_INVALID, nm + ": head_dim must be 64");
+  if (H <= 0 || H > 1024) return fail(CS_ERR_INVALID, nm + ": H must be in 1 .. 1024");
+  if (max_seqlen > 512) return fail(CS_ERR_INVALID, nm + ": texts of 1 .. 512 tokens");
+  if (ld_qkv < static_cast<int64_t>(3) * H * D || ld_qkv % 8 != 0)
+    return fail(CS_ERR_INVALID, nm + ": ld_qkv must be >= 3 H D and a multiple of 8");
+  if (!(scale > 0.0f) || std::isinf(scale)) return fail(CS_ERR_INVALID, nm + ": bad scale");
+  if (n_text == 0 || n_tok == 0 || max_seqlen == 0) return CS_OK;
+  if (!qkv || !cu_seqlens || !out) return fail(CS_ERR_INVALID, nm + ": NULL pointer");
+  if (reinterpret_cast<uintptr_t>(qkv) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
+    return fail(CS_ERR_INVALID, nm + ": qkv and out must be 16-byte aligned");
+  if (n_tok > 0x7fffffffLL) return fail(CS_ERR_INVALID, nm + ": too many tokens");
+  EncAttnParams e;
+  e.qkv = static_cast<const __bf16*>(qkv);
+  e.ldqkv = ld_qkv;
+  e.cu = cu_seqlens;
+  e.out = static_cast<__bf16*>(out);
+  e.n_tok = n_tok;
+  e.n_text = n_text;
+  e.H = H;
+  e.n_qt = (max_seqlen + kGroupRows - 1) / kGroupRows;
+  e.max_len = max_seqlen;
+  e.scale = scale;
+  const int64_t nwg = static_cast<int64_t>(n_text) * H * e.n_qt;
+  if (nwg > 0x7fffffffLL) return fail(CS_ERR_INVALID, nm + ": grid too large");
+  hipLaunchKernelGGL(encoder_attn_kernel, dim3(static_cast<uint32_t>(nwg)), dim3(kAttnThreads), 0,
+                     static_cast<hipStream_t>(stream), e);
+  return check_launch("cs_encoder_attention");
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@
 //   proposer.hip  vocab top-k (radix select) and seeded Gumbel-max sampling
 //   beam.hip      cs_beam_step / cs_beam_decode_step: whole beam decode steps in one
 //                 launch (last-arriver hand-offs, atomic welfare keys, radix select)
+//   encoder.hip   the text encoder's LayerNorms and GELU and the evaluator's cosine
+//                 similarities + welfare (fp64); its attention is in attn.hip
 //
 // No float atomics anywhere: every output is bitwise reproducible run to run.
 #pragma once

@@ -17,9 +17,24 @@ All agents of all statements are scored in ONE batched pass (per-agent prefix K/
 cs_logsoftmax_gather, cs_segment_reduce for mean log-prob AND mean prob in one
 fold) and every welfare is a cs_welfare_reduce launch over [agents, statements].
 
-Embedding cosine similarity, LLM-as-judge and comparative ranking are remote-API
-metrics outside this build: their keys are present and NaN/None,
-exactly as the reference reports them when those services are unavailable.
+The embedding block (src/evaluation.py:166-174, 232-307) runs when ``embedding_model``
+resolves to a local text encoder (runtime.get_encoder: registered, a BertModel checkpoint
+directory, or ``random:<preset>``):
+
+  statement_embedding                                 the statement's embedding (list)
+  cosine_similarity_<agent> / utility_cosine_similarity_<agent>
+                                                      1 - scipy cosine distance (:239-272)
+  egalitarian / utilitarian / log_nash _welfare_cosine and utility_*_welfare_cosine
+                                                      min / sum / sum log(max(c, 1e-9)) over
+                                                      the finite similarities       (:278-307)
+
+One encoder pass embeds every statement and every opinion (encoder.TextEncoder.embed_ids)
+and one cs_cosine_welfare launch computes all of the above in fp64.  When the embedding
+model does not resolve, the keys are present and None / NaN, exactly as the reference
+reports them when its embedding service is unavailable.
+
+LLM-as-judge and comparative ranking are remote-API metrics outside this build (SURVEY.md
+§2): their keys are present and NaN/None likewise.
 """
 from __future__ import annotations
 
@@ -83,10 +98,26 @@ class StatementEvaluator:
                     avg_p[a, si] = m_p
         return avg_lp.contiguous(), avg_p.contiguous()
 
+    def cosine_utilities(self, statements: List[str], agent_opinions: Dict[str, str]):
+        """(statement embeddings as lists, cos [A, S], welfare [3, S]) in float64 on the host, or
+        None when ``embedding_model`` resolves to no local encoder: one embed_ids pass over the
+        statements and the opinions, one cs_cosine_welfare launch."""
+        try:
+            enc, tok = runtime.get_encoder(self.embedding_model)
+        except ops.CSError:      # no local weights under this id (or no device): not served
+            return None
+        S = len(statements)
+        texts = list(statements) + list(agent_opinions.values())
+        with runtime.device_lock(enc.device):
+            E = enc.embed_ids(tok.encode_many(texts))
+            cos, wel = ops.cosine_welfare(E[:S], E[S:], eps=EPS)
+            return E[:S].double().cpu().tolist(), cos.cpu().numpy(), wel.cpu().numpy()
+
     def evaluate_statements_batched(self, statements: List[str], issue: str,
                                     agent_opinions: Dict[str, str]) -> List[Dict[str, Any]]:
         t0 = time.time()
         agents = list(agent_opinions)
+        emb = self.cosine_utilities(statements, agent_opinions)
         avg_lp, avg_p = self.agent_utilities(statements, issue, agent_opinions)
         w = {
             "egalitarian_welfare_avg_prob": ops.welfare(avg_p, "min"),
@@ -123,6 +154,16 @@ class StatementEvaluator:
             for a, aid in enumerate(agents):
                 if not math.isnan(lp_h[a, s]) and math.isfinite(lp_h[a, s]):
                     r[f"perplexity_{aid}"] = float(ppl_h[a, s])
+            if emb is not None:
+                r["statement_embedding"] = emb[0][s]
+                for a, aid in enumerate(agents):
+                    c = emb[1][a, s]
+                    r[f"cosine_similarity_{aid}"] = None if math.isnan(c) else float(c)
+                    r[f"utility_cosine_similarity_{aid}"] = r[f"cosine_similarity_{aid}"]
+                for k, kind in enumerate(("egalitarian", "utilitarian", "log_nash")):
+                    v = emb[2][k, s]
+                    r[f"{kind}_welfare_cosine"] = np.nan if math.isnan(v) else float(v)
+                    r[f"utility_{kind}_welfare_cosine"] = r[f"{kind}_welfare_cosine"]
             for kind in ("egalitarian", "utilitarian", "log_nash"):
                 val = float(w[f"{kind}_welfare_avg_prob"][s])
                 r[f"{kind}_welfare_avg_prob"] = val

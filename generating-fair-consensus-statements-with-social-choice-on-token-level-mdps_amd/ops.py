@@ -1437,3 +1437,166 @@ def schulze(x: torch.Tensor, kind: str = "rankings", valid: Optional[torch.Tenso
         if t is not None:
             out[name] = t
     return out
+
+
+# --- text encoder (csrc/encoder.hip, encoder_attn_kernel in csrc/attn.hip) ----------------
+def _vec_bf16(t: torch.Tensor, d: int, name: str) -> None:
+    if t.dtype != torch.bfloat16 or t.numel() != d or not t.is_contiguous():
+        raise CSError(f"{name} must be a contiguous bfloat16 [{d}] tensor")
+
+
+def _ragged_args(cu_seqlens: torch.Tensor, n_tok: int, max_seqlen: int):
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 1 or \
+            not cu_seqlens.is_contiguous():
+        raise CSError("cu_seqlens must be a contiguous int32 [n_text + 1] tensor")
+    if max_seqlen < 0 or max_seqlen > n_tok:
+        raise CSError("max_seqlen must be the longest text's length")
+    return int(cu_seqlens.numel()) - 1
+
+
+def embed_layer_norm(ids: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int,
+                     word_emb: torch.Tensor, pos_emb: torch.Tensor, type_emb: torch.Tensor,
+                     weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                     status: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm(word_emb[ids] + pos_emb[offset within the text] + type_emb[0]) of a ragged batch
+    (cs_embed_layer_norm): ids int32 [n_tok], cu_seqlens int32 [n_text + 1], tables bf16
+    [vocab | n_pos | >= 1, d]; returns bf16 [n_tok, d].  A text longer than the position table
+    raises; ``status`` (int32 [1], zeroed by the caller) receives -1 if an id is outside the
+    vocabulary (that row is zeros) -- without it the check is made here, with a sync."""
+    L = _lib.load()
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise CSError("ids must be a contiguous int32 [n_tok] tensor")
+    n_tok = int(ids.numel())
+    n_text = _ragged_args(cu_seqlens, n_tok, int(max_seqlen))
+    for t, name in ((word_emb, "word_emb"), (pos_emb, "pos_emb"), (type_emb, "type_emb")):
+        if t.dim() != 2 or t.dtype != torch.bfloat16 or not t.is_contiguous() or \
+                t.shape[1] != word_emb.shape[1] or t.shape[0] < 1:
+            raise CSError(f"{name} must be a contiguous bfloat16 [n, d] tensor")
+    d = int(word_emb.shape[1])
+    _vec_bf16(weight, d, "weight")
+    _vec_bf16(bias, d, "bias")
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=ids.device)
+    elif status.dtype != torch.int32 or status.numel() != 1:
+        raise CSError("status must be an int32 [1] tensor")
+    if out is None:
+        out = torch.empty(n_tok, d, dtype=torch.bfloat16, device=ids.device)
+    ldy = _rows2d(out, "out")
+    if tuple(out.shape) != (n_tok, d):
+        raise CSError("out must be [n_tok, d]")
+    _require_cuda(ids, cu_seqlens, word_emb, pos_emb, type_emb, weight, bias, status, out)
+    rc = L.cs_embed_layer_norm(ids.data_ptr(), cu_seqlens.data_ptr(), n_text, n_tok, int(max_seqlen),
+                               word_emb.data_ptr(), int(word_emb.shape[0]), pos_emb.data_ptr(),
+                               int(pos_emb.shape[0]), type_emb.data_ptr(), weight.data_ptr(),
+                               bias.data_ptr(), d, float(eps), out.data_ptr(), ldy,
+                               status.data_ptr(), _stream())
+    _lib.check(rc, "cs_embed_layer_norm")
+    if own and n_tok and int(status.item()) != 0:
+        raise CSError("cs_embed_layer_norm failed (status -1): a token id outside the vocabulary "
+                      "or a token outside every text")
+    return out
+
+
+def add_layer_norm(x: torch.Tensor, residual: Optional[torch.Tensor], weight: torch.Tensor,
+                   bias: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm(x + residual) * weight + bias (cs_add_layer_norm): [rows, d] bf16, fp32 sum and
+    statistics, one rounding."""
+    L = _lib.load()
+    ldx = _rows2d(x, "x")
+    rows, d = x.shape
+    ldr = _rows2d(residual, "residual") if residual is not None else 0
+    if residual is not None and residual.shape != x.shape:
+        raise CSError("x and residual must share one shape")
+    _vec_bf16(weight, d, "weight")
+    _vec_bf16(bias, d, "bias")
+    if out is None:
+        out = torch.empty(rows, d, dtype=torch.bfloat16, device=x.device)
+    ldy = _rows2d(out, "out")
+    if out.shape != x.shape:
+        raise CSError("out must have x's shape")
+    _require_cuda(x, residual, weight, bias, out)
+    rc = L.cs_add_layer_norm(x.data_ptr(), ldx, residual.data_ptr() if residual is not None else None,
+                             ldr, weight.data_ptr(), bias.data_ptr(), rows, d, float(eps),
+                             out.data_ptr(), ldy, _stream())
+    _lib.check(rc, "cs_add_layer_norm")
+    return out
+
+
+def gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """erf-GELU in fp32 on bf16 rows [rows, F] (cs_gelu)."""
+    L = _lib.load()
+    ldx = _rows2d(x, "x")
+    rows, F = x.shape
+    if out is None:
+        out = torch.empty(rows, F, dtype=torch.bfloat16, device=x.device)
+    ldy = _rows2d(out, "out")
+    if out.shape != x.shape:
+        raise CSError("out must have x's shape")
+    _require_cuda(x, out)
+    rc = L.cs_gelu(x.data_ptr(), ldx, rows, F, out.data_ptr(), ldy, _stream())
+    _lib.check(rc, "cs_gelu")
+    return out
+
+
+def encoder_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, n_heads: int,
+                      head_dim: int = 64, scale: Optional[float] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bidirectional attention of a ragged batch (cs_encoder_attention): qkv bf16 [n_tok, 3 H D]
+    the fused projection (q | k | v), cu_seqlens int32 [n_text + 1]; returns bf16 [n_tok, H D].
+    A token attends to its own text's keys only.  D = 64, texts of 1 .. 512 tokens."""
+    L = _lib.load()
+    ld = _rows2d(qkv, "qkv")
+    n_tok = int(qkv.shape[0])
+    n_text = _ragged_args(cu_seqlens, n_tok, int(max_seqlen))
+    H, D = int(n_heads), int(head_dim)
+    if qkv.shape[1] != 3 * H * D:
+        raise CSError("qkv must be [n_tok, 3 * n_heads * head_dim]")
+    if out is None:
+        out = torch.empty(n_tok, H * D, dtype=torch.bfloat16, device=qkv.device)
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (n_tok, H * D) or not out.is_contiguous():
+        raise CSError("out must be a contiguous bfloat16 [n_tok, H * D] tensor")
+    _require_cuda(qkv, cu_seqlens, out)
+    rc = L.cs_encoder_attention(qkv.data_ptr(), ld, cu_seqlens.data_ptr(), n_text, n_tok,
+                                int(max_seqlen), H, D,
+                                float(D ** -0.5 if scale is None else scale), out.data_ptr(),
+                                _stream())
+    _lib.check(rc, "cs_encoder_attention")
+    return out
+
+
+def cosine_welfare(E_s: torch.Tensor, E_a: torch.Tensor, valid_s: Optional[torch.Tensor] = None,
+                   valid_a: Optional[torch.Tensor] = None, eps: float = 1e-9):
+    """The evaluator's embedding utilities in one launch (cs_cosine_welfare), fp64 arithmetic:
+    E_s float32 [S, d] statement embeddings, E_a float32 [A, d] opinion embeddings, valid_* bool
+    or uint8 [S] / [A] (False: the embedding is missing).  Returns (cos [A, S], welfare [3, S])
+    float64: 1 - scipy's cosine distance (0.0 for a zero vector, NaN for a missing or non-finite
+    pair) and min / sum / sum log(max(c, eps)) over each statement's finite similarities (NaN
+    when there is none) -- src/evaluation.py:239-307."""
+    L = _lib.load()
+    for t, name in ((E_s, "E_s"), (E_a, "E_a")):
+        if t.dim() != 2 or t.dtype != torch.float32 or (t.numel() and t.stride(1) != 1):
+            raise CSError(f"{name} must be a 2-D float32 tensor with unit column stride")
+    S, d = E_s.shape
+    A = E_a.shape[0]
+    if E_a.shape[1] != d:
+        raise CSError("E_s and E_a must share the embedding width")
+
+    def vb(v, n, name):
+        if v is None:
+            return None
+        if v.dtype not in (torch.bool, torch.uint8) or tuple(v.shape) != (n,):
+            raise CSError(f"{name} must be a bool or uint8 [{n}] tensor")
+        return v.to(torch.uint8).contiguous()
+
+    valid_s, valid_a = vb(valid_s, S, "valid_s"), vb(valid_a, A, "valid_a")
+    _require_cuda(E_s, E_a, valid_s, valid_a)
+    cos = torch.empty(A, S, dtype=torch.float64, device=E_s.device)
+    wel = torch.empty(3, S, dtype=torch.float64, device=E_s.device)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731
+    rc = L.cs_cosine_welfare(ptr(E_s), E_s.stride(0) if S > 1 else d, ptr(E_a),
+                             E_a.stride(0) if A > 1 else d, ptr(valid_s), ptr(valid_a), S, A, d,
+                             float(eps), ptr(cos), ptr(wel), _stream())
+    _lib.check(rc, "cs_cosine_welfare")
+    return cos, wel

@@ -45,6 +45,7 @@ _lock = threading.RLock()
 _ENGINES: Dict[str, Tuple[ScoringEngine, CharTokenizer]] = {}
 _MODEL_DIRS: Dict[str, str] = {}
 _DEVICE_LOCKS: Dict[str, threading.RLock] = {}
+_LOADING: Dict[str, threading.Lock] = {}
 logger = logging.getLogger(__name__)
 
 _NAME_TO_PRESET = [
@@ -132,6 +133,65 @@ def clear_engines() -> None:
         _ENGINES.clear()
 
 
+# --- text encoders (the embedding model of the evaluator) ------------------------------
+_ENCODERS: Dict[str, tuple] = {}
+
+
+def register_encoder(model_identifier: str, encoder, tokenizer) -> None:
+    """Serve ``model_identifier`` (e.g. "BAAI/bge-large-en-v1.5") from this TextEncoder and its
+    tokenizer (``encode_many(texts) -> id lists``, framed and truncated)."""
+    with _lock:
+        _ENCODERS[model_identifier] = (encoder, tokenizer)
+
+
+def clear_encoders() -> None:
+    with _lock:
+        _ENCODERS.clear()
+
+
+def random_encoder(preset_name: str, device=None, seed: int = 0):
+    """Architecture-exact random-init bf16 encoder + a stand-in tokenizer (benchmarks only)."""
+    from .encoder import TextEncoder, preset as enc_preset
+    from .tokenizer import RandomIdTokenizer
+
+    cfg = enc_preset(preset_name)
+    dev = torch.device(device) if device is not None else \
+        torch.device("cuda", torch.cuda.current_device())
+    return TextEncoder(cfg, dev, seed=seed), RandomIdTokenizer(cfg.vocab, cfg.n_pos)
+
+
+def get_encoder(model_identifier: str):
+    """(TextEncoder, tokenizer) serving ``model_identifier``, resolved in get_engine's order: one
+    registered (``register_encoder``), a local BertModel checkpoint directory (the id itself,
+    ``register_model_dir`` or ``$CS_MODEL_ROOT/<id>``), ``random:<preset>`` (e.g.
+    ``random:bge-large-en-v1.5``).  Anything else raises CSError: no weights are made up."""
+    with _lock:
+        if model_identifier in _ENCODERS:
+            return _ENCODERS[model_identifier]
+        if not torch.cuda.is_available():
+            raise ops.CSError("no HIP device: the text encoder has no CPU path")
+        ld = _LOADING.setdefault("encoder:" + model_identifier, threading.Lock())
+    with ld:
+        with _lock:
+            if model_identifier in _ENCODERS:
+                return _ENCODERS[model_identifier]
+            path = _model_dir(model_identifier)
+        if path is not None:
+            from .checkpoint import load_encoder
+            ent = load_encoder(path)
+        elif model_identifier.startswith("random:"):
+            ent = random_encoder(model_identifier.split(":", 1)[1])
+        else:
+            raise ops.CSError(
+                f"no weights for embedding model {model_identifier!r}: register an encoder "
+                "(runtime.register_encoder), give a local BertModel checkpoint directory "
+                "(config.json, *.safetensors, tokenizer.json) as the id, via "
+                "runtime.register_model_dir or under $CS_MODEL_ROOT, or use 'random:<preset>'")
+        with _lock:
+            _ENCODERS[model_identifier] = ent
+        return ent
+
+
 def resolve_preset(model_identifier: str) -> str:
     name = model_identifier.lower()
     for pat, pre in _NAME_TO_PRESET[::-1] if name.startswith("tiny") else _NAME_TO_PRESET:
@@ -205,9 +265,6 @@ def use_gemm_tuning(path: Optional[str] = None) -> Optional[str]:
         _gemm_tuning = path
         logger.info("GEMM solutions from %s (PyTorch TunableOp, process-wide, read only)", path)
         return path
-
-
-_LOADING: Dict[str, threading.Lock] = {}
 
 
 def get_engine(model_identifier: str) -> Tuple[ScoringEngine, CharTokenizer]:

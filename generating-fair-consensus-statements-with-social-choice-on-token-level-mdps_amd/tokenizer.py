@@ -420,3 +420,67 @@ class BPETokenizer:
 
 def load_tokenizer(path: str, family: str, vocab_size: int = 0) -> BPETokenizer:
     return BPETokenizer(path, family=family, vocab_size=vocab_size)
+
+
+class WordPieceTokenizer:
+    """A BERT encoder's tokenizer: ``tokenizer.json`` (Hugging Face `tokenizers` format) with
+    its own normaliser and pre-tokeniser, framed ``[CLS] ... [SEP]`` and truncated to
+    ``max_len`` tokens with the final ``[SEP]`` kept (the rule of ``transformers``' and
+    sentence-transformers' BERT pipelines).  What the hosted embedding API of the reference does
+    with a text past 512 tokens (src/utils.py:376-407) is not documented: see INTEGRATION.md."""
+
+    def __init__(self, path: str, max_len: int = 512, vocab_size: int = 0) -> None:
+        import os
+
+        from tokenizers import Tokenizer
+
+        tfile = os.path.join(path, "tokenizer.json") if os.path.isdir(path) else path
+        self.tk = Tokenizer.from_file(tfile)
+        self.tk.no_truncation()
+        self.tk.no_padding()
+        self.max_len = int(max_len)
+        self.cls_id = self.tk.token_to_id("[CLS]")
+        self.sep_id = self.tk.token_to_id("[SEP]")
+        if self.cls_id is None or self.sep_id is None or self.max_len < 2:
+            raise ValueError(f"tokenizer {tfile} lacks [CLS] / [SEP]")
+        self.full_vocab = max(int(vocab_size), self.tk.get_vocab_size(with_added_tokens=True))
+
+    @property
+    def vocab_size(self) -> int:
+        return self.full_vocab
+
+    def encode(self, text: str) -> List[int]:
+        """[CLS] + word pieces + [SEP], at most max_len ids."""
+        body = self.tk.encode(text, add_special_tokens=False).ids
+        return [self.cls_id] + body[:self.max_len - 2] + [self.sep_id]
+
+    def encode_many(self, texts) -> List[List[int]]:
+        encs = self.tk.encode_batch(list(texts), add_special_tokens=False)
+        return [[self.cls_id] + e.ids[:self.max_len - 2] + [self.sep_id] for e in encs]
+
+    def tokens(self, ids: Sequence[int]) -> List[str]:
+        return [self.tk.id_to_token(int(i)) or "" for i in ids]
+
+
+class RandomIdTokenizer:
+    """Stand-in tokenizer of a ``random:`` encoder: one id per whitespace-separated word (a
+    stable hash into the vocabulary), framed and truncated as WordPieceTokenizer does.  For
+    throughput runs only -- the ids mean nothing."""
+
+    def __init__(self, vocab_size: int, max_len: int = 512) -> None:
+        self.full_vocab = int(vocab_size)
+        self.max_len = int(max_len)
+        self.cls_id, self.sep_id = 101 % self.full_vocab, 102 % self.full_vocab
+
+    @property
+    def vocab_size(self) -> int:
+        return self.full_vocab
+
+    def encode(self, text: str) -> List[int]:
+        import zlib
+
+        body = [zlib.crc32(w.encode()) % self.full_vocab for w in text.lower().split()]
+        return [self.cls_id] + body[:self.max_len - 2] + [self.sep_id]
+
+    def encode_many(self, texts) -> List[List[int]]:
+        return [self.encode(t) for t in texts]

@@ -553,6 +553,33 @@ def text_compat_last_stems(engine, tok, system: Optional[str], agent_users: Sequ
     return res
 
 
+def get_embeddings(texts: Sequence[str], model: str = "BAAI/bge-large-en-v1.5"):
+    """Batch form of get_embedding: one list of floats per text (one encoder pass for all of
+    them), or None for every text on any failure.  Never raises."""
+    texts = list(texts)
+    try:
+        if any(not isinstance(t, str) for t in texts):
+            raise TypeError("texts must be strings")
+        enc, tok = runtime.get_encoder(model)
+        with runtime.device_lock(enc.device):
+            emb = enc.embed_ids(tok.encode_many(texts)).double().cpu().tolist()
+        return emb
+    except Exception as e:  # the reference returns None on any error (src/utils.py:404-407)
+        logger.error("get_embeddings failed: %s", e)
+        return [None] * len(texts)
+
+
+def get_embedding(input_text, model="BAAI/bge-large-en-v1.5"):
+    """The embedding of ``input_text`` as a list of floats, or None on any failure
+    (src/utils.py:376-407): a forward pass of the local text encoder serving ``model``
+    (runtime.get_encoder), CLS-pooled and L2-normalised."""
+    try:
+        return get_embeddings([input_text], model)[0]
+    except Exception as e:
+        logger.error("get_embedding failed: %s", e)
+        return None
+
+
 def get_token_ids(model, text) -> Dict[str, int]:
     """{token string: id} of the chat-rendered single-message prompt (src/utils.py:466-525)."""
     try:

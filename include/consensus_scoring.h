@@ -760,6 +760,70 @@ int cs_schulze(const void* in, int in_kind, int32_t E, int32_t R, int32_t C, con
                int32_t* out_ranking, int32_t* out_untied, int32_t* out_winner, int32_t* out_status,
                cs_stream_t stream);
 
+/*
+ * Text encoder (BERT-style, post-LayerNorm: BAAI/bge-large-en-v1.5 and bge-base-en-v1.5) over
+ * a RAGGED batch with no padding: text t is tokens cu_seqlens[t] .. cu_seqlens[t + 1] - 1 of
+ * the n_tok rows (cu_seqlens int32 [n_text + 1], rising, from 0 to n_tok).  All activations and
+ * weights bf16, 16-byte aligned, leading dimensions multiples of 8; the projections between
+ * these launches are the caller's GEMMs.
+ *
+ * Replaces: the hosted embedding call get_embedding (src/utils.py:376-407), a forward pass of
+ *   the encoder, and the similarity / welfare arithmetic of src/evaluation.py:232-307.
+ *
+ * cs_embed_layer_norm — y[tok] = LayerNorm(word_emb[ids[tok]] + pos_emb[tok - cu_seqlens[t]] +
+ *   type_emb[0]) * weight + bias, summed and normalised in fp32 (mean, then the variance about
+ *   it), rounded once to bf16.  d % 8 == 0, d <= 2048.  max_seqlen (the host's longest text)
+ *   above n_pos returns CS_ERR_INVALID without a launch.  The ids live on the device, so what
+ *   only they can show is reported there: a token with an id outside [0, vocab), a position
+ *   >= n_pos or outside every text gets a zero row and *status = CS_ERR_INVALID (-1); the
+ *   caller zeroes *status (device int32) before the call and reads it when it next synchronises.
+ * cs_add_layer_norm — y = LayerNorm(x + residual) * weight + bias (residual nullable), the sum
+ *   in fp32 and never rounded on its own; y may alias x or residual.  Post-LN with a bias and
+ *   a mean, not cs_add_rms_norm.
+ * cs_gelu — y = 0.5 x (1 + erf(x / sqrt 2)) in fp32 on bf16 rows [rows][F], F % 8 == 0; y may
+ *   alias x.
+ * cs_encoder_attention — bidirectional softmax attention: out[tok][h] = softmax_k(scale q.k) v
+ *   over the keys of tok's own text only.  qkv [n_tok][ld_qkv >= 3 H D] is the fused projection
+ *   read in place (q | k | v, each [H][D], V row-major), out [n_tok][H D] contiguous.  D = 64,
+ *   1 <= text length <= max_seqlen <= 512.  bf16 MFMA 16x16x32, fp32 online softmax; one
+ *   workgroup per (text, head, 64-query tile), key blocks of 32; a text's output depends on no
+ *   byte of any other text.  A text whose cu_seqlens entries are not 0 < length <= max_seqlen
+ *   inside [0, n_tok] is skipped (nothing of it read or written).
+ */
+int cs_embed_layer_norm(const int32_t* ids, const int32_t* cu_seqlens, int32_t n_text, int64_t n_tok,
+                        int32_t max_seqlen, const void* word_emb, int32_t vocab, const void* pos_emb,
+                        int32_t n_pos, const void* type_emb, const void* weight, const void* bias,
+                        int64_t d, float eps, void* y, int64_t ldy, int32_t* status,
+                        cs_stream_t stream);
+int cs_add_layer_norm(const void* x, int64_t ldx, const void* residual, int64_t ldr,
+                      const void* weight, const void* bias, int64_t rows, int64_t d, float eps,
+                      void* y, int64_t ldy, cs_stream_t stream);
+int cs_gelu(const void* x, int64_t ldx, int64_t rows, int64_t F, void* y, int64_t ldy,
+            cs_stream_t stream);
+int cs_encoder_attention(const void* qkv, int64_t ld_qkv, const int32_t* cu_seqlens, int32_t n_text,
+                         int64_t n_tok, int32_t max_seqlen, int32_t H, int32_t D, float scale,
+                         void* out, cs_stream_t stream);
+
+/*
+ * cs_cosine_welfare — the evaluator's embedding utilities in one launch, all arithmetic fp64.
+ *
+ * E_s [S][ld_s], E_a [A][ld_a] fp32 embeddings of the statements and of the agents' opinions
+ * (first d columns); valid_s [S], valid_a [A] bytes (nullable: all valid; 0 = the embedding is
+ * missing, the reference's None).
+ *   out_cos[a][s]  = 1 - clip(1 - u.v / sqrt(u.u v.v), 0, 2)   (1 - scipy.spatial.distance.cosine)
+ *                    0.0 if u.u == 0 or v.v == 0; NaN if either is missing or the value is
+ *                    not finite (the reference's None)
+ *   out_welfare[0][s] = min, [1][s] = sum, [2][s] = sum log(max(c, eps)) over the FINITE
+ *                    out_cos[.][s], agents in order (Python's left-to-right sums); NaN when
+ *                    none is finite.
+ * out_cos [A][S], out_welfare [3][S] fp64.  One workgroup per statement; deterministic.
+ *
+ * Replaces: src/evaluation.py:239-307 (per agent, per statement, in Python).
+ */
+int cs_cosine_welfare(const float* E_s, int64_t ld_s, const float* E_a, int64_t ld_a,
+                      const uint8_t* valid_s, const uint8_t* valid_a, int32_t S, int32_t A, int64_t d,
+                      double eps, double* out_cos, double* out_welfare, cs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
