@@ -22,6 +22,9 @@ NONFINITE_SKIP, NONFINITE_REPLACE = 0, 1
 MAXIMIN_MAX_PIVOTS = 4096     # CS_MAXIMIN_MAX_PIVOTS
 SCHULZE_RANKINGS, SCHULZE_SCORES, SCHULZE_DEFEATS, SCHULZE_STRENGTHS = 0, 1, 2, 3
 SCHULZE_MAX_C, SCHULZE_MAX_R, SCHULZE_TILE = 128, 65536, 32   # csrc/schulze.hip
+# CS_KMEANS_MAX_*; the point tile, feature chunk and sum segment of csrc/cluster.hip
+KMEANS_MAX_K, KMEANS_MAX_D, KMEANS_MAX_N, KMEANS_MAX_R = 64, 4096, 1 << 20, 1024
+KMEANS_TILE, KMEANS_CHUNK, KMEANS_SEG = 64, 32, 128
 
 EXPORTED = (
     "cs_version", "cs_last_error", "cs_workspace_size", "cs_logsoftmax_gather",
@@ -38,6 +41,9 @@ EXPORTED = (
     "cs_sample_step_workspace_size", "cs_sample_step",
     "cs_embed_layer_norm", "cs_add_layer_norm", "cs_gelu", "cs_encoder_attention",
     "cs_cosine_welfare",
+    "cs_standardize_workspace_size", "cs_standardize", "cs_kmeans_workspace_size",
+    "cs_kmeans_seed", "cs_kmeans_init", "cs_kmeans_iterate", "cs_kmeans_finish",
+    "cs_nearest_rows_workspace_size", "cs_nearest_rows",
 )
 
 
@@ -183,6 +189,26 @@ def load():
     L.cs_cosine_welfare.argtypes = [vp, i64, vp, i64, vp, vp, i32, i32, i64, ctypes.c_double, vp,
                                     vp, vp]
     L.cs_cosine_welfare.restype = ctypes.c_int
+    f64, sz = ctypes.c_double, ctypes.c_size_t
+    L.cs_standardize_workspace_size.argtypes = [i32, i32]
+    L.cs_standardize_workspace_size.restype = sz
+    L.cs_standardize.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, vp, sz, vp]
+    L.cs_standardize.restype = ctypes.c_int
+    L.cs_kmeans_workspace_size.argtypes = [i32, i32, i32, i32]
+    L.cs_kmeans_workspace_size.restype = sz
+    L.cs_kmeans_seed.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.cs_kmeans_seed.restype = ctypes.c_int
+    L.cs_kmeans_init.argtypes = [vp, i64, i32, i32, i32, i32, f64, vp, vp, sz, vp]
+    L.cs_kmeans_init.restype = ctypes.c_int
+    L.cs_kmeans_iterate.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, i32, i32, vp, sz, vp]
+    L.cs_kmeans_iterate.restype = ctypes.c_int
+    L.cs_kmeans_finish.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   vp, sz, vp]
+    L.cs_kmeans_finish.restype = ctypes.c_int
+    L.cs_nearest_rows_workspace_size.argtypes = [i32, i32]
+    L.cs_nearest_rows_workspace_size.restype = sz
+    L.cs_nearest_rows.argtypes = [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, sz, vp]
+    L.cs_nearest_rows.restype = ctypes.c_int
     _lib = L
     return L
 

@@ -16,6 +16,7 @@ import json
 import operator
 import os
 import threading
+import time
 from typing import Dict, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -1600,3 +1601,191 @@ def cosine_welfare(E_s: torch.Tensor, E_a: torch.Tensor, valid_s: Optional[torch
                              float(eps), ptr(cos), ptr(wel), _stream())
     _lib.check(rc, "cs_cosine_welfare")
     return cos, wel
+
+
+# --- clustering (csrc/cluster.hip): StandardScaler, KMeans, nearest rows, all fp64 -----------
+def _f64_rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A 2-D device tensor as contiguous float64 rows (a float32 input is widened)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_floating_point():
+        raise CSError(f"{name} must be a 2-D floating-point tensor")
+    _require_cuda(t)
+    return t.to(torch.float64).contiguous()
+
+
+def _kmeans_limits(n: int, d: int, k: int = 1, R: int = 1) -> None:
+    if not (1 <= n <= _lib.KMEANS_MAX_N and 1 <= d <= _lib.KMEANS_MAX_D):
+        raise CSError(f"need 1 <= n <= {_lib.KMEANS_MAX_N} and 1 <= d <= {_lib.KMEANS_MAX_D}, "
+                      f"got n {n}, d {d}")
+    if not (1 <= k <= _lib.KMEANS_MAX_K and 1 <= R <= _lib.KMEANS_MAX_R):
+        raise CSError(f"need 1 <= k <= {_lib.KMEANS_MAX_K} and 1 <= restarts <= "
+                      f"{_lib.KMEANS_MAX_R}, got k {k}, restarts {R}")
+    if k > n:
+        raise CSError(f"need k <= n, got k {k}, n {n}")
+
+
+def _scratch(nbytes: int, device: torch.device) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def standardize(X: torch.Tensor):
+    """StandardScaler().fit_transform on the device (cs_standardize), fp64: returns (Z, mean,
+    scale) with the population variance and scale 1 for a constant feature (scikit-learn's rule,
+    var <= n eps var + (n mean eps)^2).  A float32 X is widened first."""
+    L = _lib.load()
+    X = _f64_rows(X, "X")
+    n, d = X.shape
+    _kmeans_limits(n, d)
+    Z = torch.empty_like(X)
+    mean = torch.empty(d, dtype=torch.float64, device=X.device)
+    scale = torch.empty_like(mean)
+    ws = _scratch(L.cs_standardize_workspace_size(n, d), X.device)
+    rc = L.cs_standardize(X.data_ptr(), d, n, d, Z.data_ptr(), d, mean.data_ptr(), scale.data_ptr(),
+                          ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "cs_standardize")
+    return Z, mean, scale
+
+
+def kmeans_trials(k: int) -> int:
+    """k-means++ candidates per centre, scikit-learn's 2 + int(log k)."""
+    return 2 + int(np.log(k))
+
+
+def _seed_draws(first, u, k: int):
+    first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+    R, T = first.size, kmeans_trials(k)
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    if u.shape != (R, k - 1, T):
+        raise CSError(f"u must be [{R}, {k - 1}, {T}] (restarts, k - 1, 2 + int(log k)), got "
+                      f"{u.shape}")
+    return first, u, R, T
+
+
+def kmeans_seed(Z: torch.Tensor, k: int, first, u, *, _ws: Optional[torch.Tensor] = None):
+    """k-means++ of R restarts at once (cs_kmeans_seed) from numpy's draws: Z float64 [n, d]
+    (centred), first [R] the first centres' rows, u [R, k - 1, T] uniforms in [0, 1) (host
+    arrays).  Returns (centers [R, k, d] float64, indices [R, k] int32) on the device."""
+    L = _lib.load()
+    Z = _f64_rows(Z, "Z")
+    n, d = Z.shape
+    first, u, R, T = _seed_draws(first, u, k)
+    _kmeans_limits(n, d, k, R)
+    dev = Z.device
+    ws = _ws if _ws is not None else _scratch(L.cs_kmeans_workspace_size(n, d, k, R), dev)
+    first_d = torch.from_numpy(first).to(dev)
+    u_d = torch.from_numpy(u).to(dev) if u.size else None
+    centers = torch.empty(R, k, d, dtype=torch.float64, device=dev)
+    indices = torch.empty(R, k, dtype=torch.int32, device=dev)
+    rc = L.cs_kmeans_seed(Z.data_ptr(), d, n, d, k, R, T, first.ctypes.data,
+                          u.ctypes.data if u.size else None, first_d.data_ptr(),
+                          None if u_d is None else u_d.data_ptr(), centers.data_ptr(),
+                          indices.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "cs_kmeans_seed")
+    return centers, indices
+
+
+def kmeans(Zs: torch.Tensor, k: int, first=None, u=None, *, n_init: Optional[int] = None,
+           init: Optional[torch.Tensor] = None, max_iter: int = 300, tol: float = 1e-4,
+           poll_every: int = 8, timings: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+    """The whole fit of KMeans on the device, fp64: Zs [n, d] is centred by its column mean,
+    R = len(first) restarts are seeded (kmeans_seed) or started from ``init`` ([k, d] or
+    [R, k, d], uncentred), iterated together (cs_kmeans_iterate: a finished restart's workgroups
+    exit; ``live`` is read back every ``poll_every`` iterations, the only host syncs), and one
+    restart is chosen per group of ``n_init`` consecutive restarts (default: all of them) by
+    scikit-learn's sequential rule (cs_kmeans_finish).
+    Returns labels [G, n] int32, centers [G, k, d] (uncentred), best [G], inertia [R],
+    n_iter [R], done [R] (1 labels repeated, 2 tolerance or max_iter), indices [R, k] (-1 with
+    init), mean [d], iterations (enqueued per restart).  ``timings`` (a dict) asks for the wall
+    clock of each phase in ms, taken with a device synchronise at each phase's end."""
+    L = _lib.load()
+    Zs = _f64_rows(Zs, "Zs")
+    n, d = Zs.shape
+    dev = Zs.device
+    if max_iter < 1 or poll_every < 1:
+        raise CSError("need max_iter >= 1 and poll_every >= 1")
+    if init is not None:
+        C0 = init.to(torch.float64)
+        _require_cuda(C0)
+        if C0.dim() == 2:
+            C0 = C0[None]
+        if C0.dim() != 3 or tuple(C0.shape[1:]) != (k, d):
+            raise CSError(f"init must be [{k}, {d}] or [R, {k}, {d}]")
+        R = C0.shape[0]
+    else:
+        if first is None or (u is None and k > 1):
+            raise CSError("kmeans needs the draws (first, u) or init")
+        if u is None:
+            u = np.zeros((len(first), 0, kmeans_trials(k)))
+        first, u, R, _ = _seed_draws(first, u, k)
+    _kmeans_limits(n, d, k, R)
+    n_init = R if n_init is None else int(n_init)
+    if n_init < 1 or R % n_init:
+        raise CSError(f"the restarts ({R}) must be a multiple of n_init ({n_init})")
+    G = R // n_init
+    clock = [0.0]
+
+    def lap(name):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            if name:
+                timings[name] = timings.get(name, 0.0) + (now - clock[0]) * 1e3
+            clock[0] = now
+
+    lap(None)
+    mean = Zs.mean(dim=0)
+    Z = (Zs - mean).contiguous()
+    ws = _scratch(L.cs_kmeans_workspace_size(n, d, k, R), dev)
+    if init is not None:
+        centers = (C0 - mean).contiguous()
+        indices = torch.full((R, k), -1, dtype=torch.int32, device=dev)
+    else:
+        centers, indices = kmeans_seed(Z, k, first, u, _ws=ws)
+    lap("seed_ms")
+    state = torch.empty(2 * R + 1, dtype=torch.int32, device=dev)
+    st = _stream()
+    wsa = (ws.data_ptr(), ws.numel(), st)
+    _lib.check(L.cs_kmeans_init(Z.data_ptr(), d, n, d, k, R, float(tol), state.data_ptr(), *wsa),
+               "cs_kmeans_init")
+    enq = 0
+    while enq < max_iter:
+        steps = min(poll_every, max_iter - enq)
+        _lib.check(L.cs_kmeans_iterate(Z.data_ptr(), d, n, d, k, R, centers.data_ptr(),
+                                       state.data_ptr(), steps, max_iter, *wsa), "cs_kmeans_iterate")
+        enq += steps
+        if int(state[2 * R].item()) == 0:
+            break
+    lap("iterate_ms")
+    best = torch.empty(G, dtype=torch.int32, device=dev)
+    labels = torch.empty(G, n, dtype=torch.int32, device=dev)
+    out_c = torch.empty(G, k, d, dtype=torch.float64, device=dev)
+    inertia = torch.empty(R, dtype=torch.float64, device=dev)
+    n_iter = torch.empty(R, dtype=torch.int32, device=dev)
+    rc = L.cs_kmeans_finish(Z.data_ptr(), d, n, d, k, R, n_init, centers.data_ptr(), mean.data_ptr(),
+                            state.data_ptr(), best.data_ptr(), labels.data_ptr(), out_c.data_ptr(),
+                            inertia.data_ptr(), n_iter.data_ptr(), *wsa)
+    _lib.check(rc, "cs_kmeans_finish")
+    lap("finish_ms")
+    return {"labels": labels, "centers": out_c, "best": best, "inertia": inertia, "n_iter": n_iter,
+            "done": state[:R].clone(), "indices": indices, "mean": mean, "iterations": enq}
+
+
+def nearest_rows(Q: torch.Tensor, X: torch.Tensor):
+    """For each row of Q the index of the nearest row of X (fp64 squared distance, the first
+    lowest index on ties) and the Euclidean distance (cs_nearest_rows): (int32 [q], float64 [q]).
+    sklearn.metrics.pairwise_distances_argmin_min(Q, X)."""
+    L = _lib.load()
+    Q, X = _f64_rows(Q, "Q"), _f64_rows(X, "X")
+    q, d = Q.shape
+    n = X.shape[0]
+    if X.shape[1] != d:
+        raise CSError("Q and X must share the feature width")
+    _kmeans_limits(n, d)
+    if not 1 <= q <= _lib.KMEANS_MAX_N:
+        raise CSError(f"need 1 <= q <= {_lib.KMEANS_MAX_N}")
+    idx = torch.empty(q, dtype=torch.int32, device=X.device)
+    dist = torch.empty(q, dtype=torch.float64, device=X.device)
+    ws = _scratch(L.cs_nearest_rows_workspace_size(q, n), X.device)
+    rc = L.cs_nearest_rows(Q.data_ptr(), d, q, X.data_ptr(), d, n, d, idx.data_ptr(),
+                           dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "cs_nearest_rows")
+    return idx, dist

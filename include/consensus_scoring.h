@@ -824,6 +824,87 @@ int cs_cosine_welfare(const float* E_s, int64_t ld_s, const float* E_a, int64_t 
                       const uint8_t* valid_s, const uint8_t* valid_a, int32_t S, int32_t A, int64_t d,
                       double eps, double* out_cos, double* out_welfare, cs_stream_t stream);
 
+/*
+ * Clustering of embeddings: StandardScaler, KMeans and the row nearest each centre, scikit-learn's
+ * decisions restated, all arithmetic fp64 (csrc/cluster.hip).  Matrices are row-major doubles with
+ * a leading dimension >= d, 8-byte aligned.  Kernel boundaries are the only grid-wide
+ * synchronisation; every sum over points is folded in a fixed order (per-tile partials, then the
+ * tiles in order) and there is no floating-point atomic, so two runs are bitwise equal.
+ *
+ * Limits (CSError / CS_ERR_INVALID above them): k <= 64, d <= 4096, n <= 2^20, R <= 1024.
+ *
+ * cs_standardize — Z = (X - mean) / scale per column.  mean = sum / n; var = (sum (x - mean)^2 -
+ *   (sum (x - mean))^2 / n) / n (ddof 0); scale = sqrt(var), or 1 for a constant feature:
+ *   var <= n eps var + (n mean eps)^2, eps = 2^-52.  Z may alias X.
+ *
+ * cs_kmeans_seed — k-means++ for R restarts at once.  Z is centred by the caller.  first [R]
+ *   int32 rows, u [R][k - 1][T] doubles in [0, 1), T = 2 + int(log k): the draws of
+ *   numpy's RandomState, made by the caller.  Both are given twice: on the host (checked here,
+ *   before any launch) and on the device (read by the kernels).  Per restart: the first centre is
+ *   Z[first]; closest[i] the squared distance of row i to it, pot = sum closest; for
+ *   c = 1 .. k - 1 the candidates are min(searchsorted(cumsum(closest), u pot, side=left), n - 1),
+ *   the one with the smallest sum of min(closest, dist^2(candidate, .)) is kept (first on ties)
+ *   and closest, pot become its.  centers [R][k][d], indices [R][k].
+ *
+ * cs_kmeans_init — labels = -1, state = running, and tol_abs = mean(var(Z, axis 0)) * tol in the
+ *   workspace.  state is int32 [2 R + 1]: done [R] (0 running, 1 the labels repeated, 2 the
+ *   tolerance or max_iter ended it), n_iter [R], live (the number of restarts still running).
+ *
+ * cs_kmeans_iterate — n_steps Lloyd iterations of every running restart; the workgroups of a
+ *   finished restart exit, so the host enqueues steps blindly and polls `live`.  One iteration:
+ *   label = the first lowest squared distance to the old centres; per-cluster sums and counts;
+ *   empty clusters, in increasing id, take the points farthest from their assigned old centre,
+ *   farthest first, the lower index among equal distances (sum[o] -= z, sum[e] = z, count[e] = 1,
+ *   count[o] -= 1; labels unchanged; nothing moves if that largest distance is 0);
+ *   centre = sum * (1 / count), a cluster still empty takes the first largest cluster's row;
+ *   shift = sum_c |new_c - old_c|^2.  Done if the labels equal the previous iteration's (1), else
+ *   if shift <= tol_abs or n_iter == max_iter (2).  centers [R][k][d] is updated in place.
+ *
+ * cs_kmeans_finish — restarts not done by repeated labels are labelled once more against their
+ *   final centres; inertia[r] = sum_i |z_i - c_label(i)|^2; per group of n_init consecutive
+ *   restarts (R % n_init == 0), restart r replaces the incumbent if its inertia is lower and its
+ *   labels are not the incumbent's partition renamed.  out_best [R / n_init] (index within the
+ *   group), out_labels [R / n_init][n], out_centers [R / n_init][k][d] (mean [d], nullable, added
+ *   back), out_inertia [R], out_n_iter [R].
+ *
+ * cs_nearest_rows — for each of q rows of Q the index of the nearest of X's n rows (squared
+ *   distance, the first lowest index on ties) and the Euclidean distance.
+ *
+ * The three cs_kmeans_* calls of one fit share one workspace of cs_kmeans_workspace_size bytes,
+ * 16-byte aligned; nothing else may touch it between them.
+ *
+ * Replaces: sklearn's StandardScaler, KMeans(n_init, random_state) and
+ *   pairwise_distances_argmin_min as data/cluster_habermas_issues.py:118-160 calls them.
+ */
+#define CS_KMEANS_MAX_K 64
+#define CS_KMEANS_MAX_D 4096
+#define CS_KMEANS_MAX_N 1048576
+#define CS_KMEANS_MAX_R 1024
+size_t cs_standardize_workspace_size(int32_t n, int32_t d);
+int cs_standardize(const double* X, int64_t ldx, int32_t n, int32_t d, double* Z, int64_t ldz,
+                   double* mean, double* scale, void* workspace, size_t workspace_bytes,
+                   cs_stream_t stream);
+size_t cs_kmeans_workspace_size(int32_t n, int32_t d, int32_t k, int32_t R);
+int cs_kmeans_seed(const double* Z, int64_t ldz, int32_t n, int32_t d, int32_t k, int32_t R,
+                   int32_t T, const int32_t* first_host, const double* u_host, const int32_t* first,
+                   const double* u, double* centers, int32_t* indices, void* workspace,
+                   size_t workspace_bytes, cs_stream_t stream);
+int cs_kmeans_init(const double* Z, int64_t ldz, int32_t n, int32_t d, int32_t k, int32_t R,
+                   double tol, int32_t* state, void* workspace, size_t workspace_bytes,
+                   cs_stream_t stream);
+int cs_kmeans_iterate(const double* Z, int64_t ldz, int32_t n, int32_t d, int32_t k, int32_t R,
+                      double* centers, int32_t* state, int32_t n_steps, int32_t max_iter,
+                      void* workspace, size_t workspace_bytes, cs_stream_t stream);
+int cs_kmeans_finish(const double* Z, int64_t ldz, int32_t n, int32_t d, int32_t k, int32_t R,
+                     int32_t n_init, const double* centers, const double* mean, const int32_t* state,
+                     int32_t* out_best, int32_t* out_labels, double* out_centers, double* out_inertia,
+                     int32_t* out_n_iter, void* workspace, size_t workspace_bytes,
+                     cs_stream_t stream);
+size_t cs_nearest_rows_workspace_size(int32_t q, int32_t n);
+int cs_nearest_rows(const double* Q, int64_t ldq, int32_t q, const double* X, int64_t ldx, int32_t n,
+                    int32_t d, int32_t* out_index, double* out_dist, void* workspace,
+                    size_t workspace_bytes, cs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
