@@ -68,9 +68,9 @@ def _device_rows(embeddings, k: Optional[int] = None, n_init: int = 1) -> torch.
         raise ValueError(f"embeddings must be a 2-D floating-point array, got {tuple(E.shape)}")
     if k is not None:
         _check_fit(E.shape[0], k, n_init)
-    if not torch.cuda.is_available() and not E.is_cuda:
-        raise ops.CSError("clustering runs on the GPU; there is no CPU path")
-    return E.cuda() if not E.is_cuda else E
+    if E.is_cuda:
+        return E
+    return E.to(ops.default_device("clustering runs on the GPU; there is no CPU path"))
 
 
 def _check_fit(n: int, k: int, n_init: int) -> None:

@@ -45,9 +45,7 @@ from . import ops
 
 
 def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise ops.CSError("core: the GPU path needs a HIP device (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return ops.default_device("core: the GPU path needs a HIP device (no CPU fallback)")
 
 
 def generate_params(B, L, d, n_agents, seed=123):

@@ -33,7 +33,6 @@ constexpr int kKmDistLds = kKmTile * (kKmChunk + 1) + 64 * kKmChunk;   // double
 
 static_assert(kKmDistLds == kKmTile * 65, "the distance matrix reuses the staging buffers");
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t up16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
 
 // ---------------------------------------------------------------------------------------------
@@ -837,8 +836,6 @@ __global__ void km_nearest_fold_kernel(int32_t q, int32_t tiles, const double* _
 // ---------------------------------------------------------------------------------------------
 // argument checks
 // ---------------------------------------------------------------------------------------------
-inline bool misaligned(const void* p, int a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-
 int check_matrix(const std::string& w, const char* name, const void* p, int64_t ld, int32_t d) {
   if (!p) return fail(CS_ERR_INVALID, w + name + " is NULL");
   if (misaligned(p, 8)) return fail(CS_ERR_INVALID, w + name + " must be 8-byte aligned");

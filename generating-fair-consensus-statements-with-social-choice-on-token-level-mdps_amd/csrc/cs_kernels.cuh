@@ -58,6 +58,24 @@ inline int check_launch(const char* what) {
   return CS_OK;
 }
 
+// an optional pointer may be NULL: NULL is aligned
+inline bool misaligned(const void* p, int a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Launch of a kernel that may take more dynamic LDS than the default 64 KiB: the limit is raised
+// to `limit` once per process and kernel (a template argument: one static per instantiation)
+template <auto Kernel, typename... Args>
+inline void launch_big_lds(size_t limit, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                           Args... args) {
+  if (lds > 64 * 1024) {
+    static const hipError_t raised =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(limit));
+    (void)raised;  // a refusal shows as the launch's own error
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+}
+
 // Argument checks shared by the entry points that stream whole logits rows
 // (cs_logsoftmax_gather, cs_vocab_topk, cs_vocab_sample, cs_sample_step, cs_beam_step,
 // cs_beam_decode_step).
@@ -70,7 +88,7 @@ inline int check_logits(const char* fn, int dtype, int64_t vocab, int64_t ld) {
   return CS_OK;
 }
 inline int check_elt_aligned(const char* fn, const void* logits, int dtype) {
-  if (reinterpret_cast<uintptr_t>(logits) % (dtype == CS_F32 ? 4 : 2) != 0)
+  if (misaligned(logits, dtype == CS_F32 ? 4 : 2))
     return fail(CS_ERR_INVALID, std::string(fn) + ": logits not element-aligned");
   return CS_OK;
 }
@@ -83,7 +101,7 @@ inline int check_softcap(const char* fn, float softcap) {
 inline int check_workspace(const char* fn, const void* ws, size_t have, size_t need, int align = 8) {
   if (!ws || have < need)
     return fail(CS_ERR_WORKSPACE, std::string(fn) + ": workspace smaller than its workspace_size()");
-  if (reinterpret_cast<uintptr_t>(ws) % align != 0)
+  if (misaligned(ws, align))
     return fail(CS_ERR_WORKSPACE, std::string(fn) + ": workspace not 8-byte aligned");
   return CS_OK;
 }
@@ -165,6 +183,67 @@ __device__ __forceinline__ uint16_t bf16_bits(float f) {
   return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 __device__ __forceinline__ __bf16 to_bf16(float f) { return __builtin_bit_cast(__bf16, bf16_bits(f)); }
+__device__ __forceinline__ float bf(uint16_t v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
+typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));   // one 16-byte vector of bf16 bits
+
+// Workgroup reductions.  fp32 sum: wave64 butterfly, then the BLOCK / 64 wave sums in wave order
+// (the one order of every norm, so a norm is bitwise the same in every kernel that uses it).
+// red holds BLOCK / 64 floats; a second sum before a barrier needs its own.
+template <int BLOCK>
+__device__ __forceinline__ float block_sum(float ss, float* red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  float tot = 0.0f;
+#pragma unroll
+  for (int i = 0; i < BLOCK / 64; ++i) tot += red[i];
+  return tot;
+}
+
+// one step of an fp64 wave butterfly, and the sum over the first `width` lanes (a power of two
+// >= the lanes that hold a term; the others hold 0) from the nearest partner outwards: every
+// one of those lanes returns the same bits
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  return __shfl_xor(v, mask, 64);
+}
+__device__ __forceinline__ double wave_sum_f64(double v, int width = 64) {
+  for (int k = 1; k < width; k <<= 1) v += shfl_xor_f64(v, k);
+  return v;
+}
+
+// The workgroup's best of every thread's (value, index) pair under Better(v, j, v0, j0),
+// returned to every thread: wave butterfly, lane 0 of each wave to wg / wj [BLOCK / 64], a
+// barrier, then the waves' bests folded in wave order.  Better must be a total order on the
+// pairs (ties in the value broken by the index), which is why the result does not depend on
+// the shape of the reduction.  Pairs go in and out by value, so they stay in registers.
+struct ArgBest { double v; int32_t j; };
+template <int BLOCK, auto Better>
+__device__ __forceinline__ ArgBest block_argbest(double bg, int32_t bj, double* wg, int32_t* wj) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int k = 1; k < 64; k <<= 1) {
+    const double og = shfl_xor_f64(bg, k);
+    const int32_t oj = __shfl_xor(bj, k, 64);
+    if (Better(og, oj, bg, bj)) {
+      bg = og;
+      bj = oj;
+    }
+  }
+  if (lane == 0) {
+    wg[wave] = bg;
+    wj[wave] = bj;
+  }
+  __syncthreads();
+  bg = wg[0];
+  bj = wj[0];
+  for (int w = 1; w < BLOCK / 64; ++w) {
+    if (Better(wg[w], wj[w], bg, bj)) {
+      bg = wg[w];
+      bj = wj[w];
+    }
+  }
+  return ArgBest{bg, bj};
+}
 
 // Gemma-2 final-logit soft-capping, cap * tanh(x / cap), written through one exp2 and
 // the hardware reciprocal (1 ulp) so the vocab stream and the target gather use the

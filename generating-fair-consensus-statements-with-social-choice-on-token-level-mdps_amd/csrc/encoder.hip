@@ -17,24 +17,8 @@
 
 namespace {
 
-typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float bf(uint16_t v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
-
 constexpr int kEncThreads = 256;
 constexpr int kEncMaxD = 8 * kEncThreads;   // one 16-byte vector per thread
-
-// the row's sum over the workgroup: wave64 butterfly, then the four wave sums in wave order
-__device__ __forceinline__ float enc_row_sum(float ss, float* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  float tot = 0.0f;
-#pragma unroll
-  for (int i = 0; i < kEncThreads / 64; ++i) tot += red[i];
-  return tot;
-}
 
 // LayerNorm of the row whose 8 elements x[] this thread holds (has: v < d / 8), two passes
 // over registers: mean, then the variance about it (a constant row has variance exactly 0).
@@ -52,7 +36,7 @@ __device__ __forceinline__ void layer_norm_row(float (&x)[8], bool has, int v, i
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += x[e];
   }
-  const float mean = enc_row_sum(s, red[0]) / static_cast<float>(d);
+  const float mean = block_sum<kEncThreads>(s, red[0]) / static_cast<float>(d);
   float ss = 0.0f;
   if (has) {
 #pragma unroll
@@ -61,7 +45,7 @@ __device__ __forceinline__ void layer_norm_row(float (&x)[8], bool has, int v, i
       ss = fmaf(x[e], x[e], ss);
     }
   }
-  const float rstd = 1.0f / sqrtf(enc_row_sum(ss, red[1]) / static_cast<float>(d) + eps);
+  const float rstd = 1.0f / sqrtf(block_sum<kEncThreads>(ss, red[1]) / static_cast<float>(d) + eps);
   if (has) {
     u16x8 out;
 #pragma unroll
@@ -156,7 +140,7 @@ __device__ __forceinline__ void sum3(double (&v)[3], double (*red)[3]) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+    for (int o = 32; o >= 1; o >>= 1) v[k] += shfl_xor_f64(v[k], o);
   }
   __syncthreads();   // the last totals are read
   if ((threadIdx.x & 63) == 0) {
@@ -233,8 +217,6 @@ int check_ln_shape(const std::string& nm, int64_t rows, int64_t d) {
   return CS_OK;
 }
 
-inline bool misaligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -256,8 +238,8 @@ int cs_embed_layer_norm(const int32_t* ids, const int32_t* cu_seqlens, int32_t n
     return fail(CS_ERR_INVALID, nm + ": NULL pointer");
   if (!(eps >= 0.0f)) return fail(CS_ERR_INVALID, nm + ": eps must be >= 0");
   if (ldy < d || ldy % 8) return fail(CS_ERR_INVALID, nm + ": ldy must be >= d and a multiple of 8");
-  if (misaligned16(word_emb) || misaligned16(pos_emb) || misaligned16(type_emb) || misaligned16(weight) ||
-      misaligned16(bias) || misaligned16(y))
+  if (misaligned(word_emb, 16) || misaligned(pos_emb, 16) || misaligned(type_emb, 16) ||
+      misaligned(weight, 16) || misaligned(bias, 16) || misaligned(y, 16))
     return fail(CS_ERR_INVALID, nm + ": tables and output must be 16-byte aligned");
   hipLaunchKernelGGL(embed_ln_kernel, dim3(static_cast<uint32_t>(n_tok)), dim3(kEncThreads), 0,
                      static_cast<hipStream_t>(stream), ids, cu_seqlens, n_text,
@@ -277,8 +259,8 @@ int cs_add_layer_norm(const void* x, int64_t ldx, const void* residual, int64_t 
   if (!(eps >= 0.0f)) return fail(CS_ERR_INVALID, nm + ": eps must be >= 0");
   if (ldx < d || ldy < d || ldx % 8 || ldy % 8 || (residual && (ldr < d || ldr % 8)))
     return fail(CS_ERR_INVALID, nm + ": leading dimensions must be >= d and multiples of 8");
-  if (misaligned16(x) || misaligned16(residual) || misaligned16(weight) || misaligned16(bias) ||
-      misaligned16(y))
+  if (misaligned(x, 16) || misaligned(residual, 16) || misaligned(weight, 16) ||
+      misaligned(bias, 16) || misaligned(y, 16))
     return fail(CS_ERR_INVALID, nm + ": pointers must be 16-byte aligned");
   hipLaunchKernelGGL(add_ln_kernel, dim3(static_cast<uint32_t>(rows)), dim3(kEncThreads), 0,
                      static_cast<hipStream_t>(stream), static_cast<const uint16_t*>(x), ldx,
@@ -294,8 +276,8 @@ int cs_gelu(const void* x, int64_t ldx, int64_t rows, int64_t F, void* y, int64_
   if (!x || !y) return fail(CS_ERR_INVALID, "cs_gelu: NULL pointer");
   if (F % 8 || ldx % 8 || ldy % 8 || ldx < F || ldy < F)
     return fail(CS_ERR_INVALID, "cs_gelu: F and leading dimensions must be multiples of 8, >= F");
-  if (misaligned16(x) || misaligned16(y)) return fail(CS_ERR_INVALID, "cs_gelu: pointers must be 16-byte aligned");
-  const int64_t nb = (F / 8 + kEncThreads - 1) / kEncThreads;
+  if (misaligned(x, 16) || misaligned(y, 16)) return fail(CS_ERR_INVALID, "cs_gelu: pointers must be 16-byte aligned");
+  const int64_t nb = cdiv(F / 8, kEncThreads);
   if (rows * nb > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_gelu: grid too large");
   hipLaunchKernelGGL(gelu_kernel, dim3(static_cast<uint32_t>(rows * nb)), dim3(kEncThreads), 0,
                      static_cast<hipStream_t>(stream), static_cast<const uint16_t*>(x), ldx, F,
@@ -312,8 +294,7 @@ int cs_cosine_welfare(const float* E_s, int64_t ld_s, const float* E_a, int64_t 
     return fail(CS_ERR_INVALID, "cs_cosine_welfare: NULL pointer");
   if (ld_s < d || (A > 0 && ld_a < d)) return fail(CS_ERR_INVALID, "cs_cosine_welfare: leading dimension < d");
   if (!(eps > 0.0)) return fail(CS_ERR_INVALID, "cs_cosine_welfare: eps must be > 0");
-  if (reinterpret_cast<uintptr_t>(E_s) % 4 || reinterpret_cast<uintptr_t>(E_a) % 4 ||
-      reinterpret_cast<uintptr_t>(out_cos) % 8 || reinterpret_cast<uintptr_t>(out_welfare) % 8)
+  if (misaligned(E_s, 4) || misaligned(E_a, 4) || misaligned(out_cos, 8) || misaligned(out_welfare, 8))
     return fail(CS_ERR_INVALID, "cs_cosine_welfare: misaligned pointer");
   hipLaunchKernelGGL(cosine_welfare_kernel, dim3(static_cast<uint32_t>(S)), dim3(kEncThreads), 0,
                      static_cast<hipStream_t>(stream), E_s, ld_s, E_a, ld_a, valid_s, valid_a, S, A, d,

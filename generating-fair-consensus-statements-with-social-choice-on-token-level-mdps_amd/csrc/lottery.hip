@@ -35,15 +35,9 @@ constexpr double kGolden = 0x1.3c6ef372fe95p-1;  // (sqrt(5) - 1) / 2 in fp64, c
 constexpr size_t kLotLdsBytes = 144 * 1024;
 constexpr int kLotWideM = 4096;               // above this many columns: 1024-thread workgroups
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-  return __shfl_xor(v, mask, 64);
-}
-
-// sum over the first `width` lanes (a power of two >= the lanes that hold a term; the others
-// hold 0), broadcast from lane 0: every lane returns the same bits
+// wave_sum_f64 over `width` lanes, broadcast from lane 0: the same bits in every lane
 __device__ __forceinline__ double wave_sum_bcast(double v, int width) {
-  for (int k = 1; k < width; k <<= 1) v += shfl_xor_f64(v, k);
-  return __shfl(v, 0, 64);
+  return __shfl(wave_sum_f64(v, width), 0, 64);
 }
 
 // (g, j) ordered by g descending, then j ascending: np.argmax's first maximum
@@ -72,20 +66,19 @@ __device__ __forceinline__ void lot_row_dots(LotSmem& S, const double* __restric
       const double u = STAGED ? smU[static_cast<int64_t>(i) * m + j] : Ug[i * ldu + j];
       acc += u * p[j];
     }
-    for (int k = 1; k < 64; k <<= 1) acc += shfl_xor_f64(acc, k);
+    acc = wave_sum_f64(acc);
     if (lane == 0) S.a[i] = acc;
   }
 }
 
 // The block's argmax_j of g_j = sum_i U[i,j] / a_i (lowest j on ties), returned to every thread
 template <int BLOCK, bool STAGED>
-__device__ __forceinline__ void lot_gradient_argmax(LotSmem& S, const double* __restrict__ Ug,
-                                                    const double* smU, int32_t A, int32_t m,
-                                                    int64_t ldu, double& g_best, int32_t& j_best) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ ArgBest lot_gradient_argmax(LotSmem& S, const double* __restrict__ Ug,
+                                                       const double* smU, int32_t A, int32_t m,
+                                                       int64_t ldu) {
   double bg = -INFINITY;
   int32_t bj = 0x7fffffff;
-  for (int32_t j = tid; j < m; j += BLOCK) {
+  for (int32_t j = threadIdx.x; j < m; j += BLOCK) {
     double g = 0.0;
     for (int32_t i = 0; i < A; ++i) {
       const double u = STAGED ? smU[static_cast<int64_t>(i) * m + j] : Ug[i * ldu + j];
@@ -96,29 +89,8 @@ __device__ __forceinline__ void lot_gradient_argmax(LotSmem& S, const double* __
       bj = j;
     }
   }
-  for (int k = 1; k < 64; k <<= 1) {
-    const double og = shfl_xor_f64(bg, k);
-    const int32_t oj = __shfl_xor(bj, k, 64);
-    if (lot_better(og, oj, bg, bj)) {
-      bg = og;
-      bj = oj;
-    }
-  }
-  if (lane == 0) {
-    S.wg[wave] = bg;
-    S.wj[wave] = bj;
-  }
-  __syncthreads();
-  bg = S.wg[0];
-  bj = S.wj[0];
-  for (int w = 1; w < BLOCK / 64; ++w) {
-    if (lot_better(S.wg[w], S.wj[w], bg, bj)) {
-      bg = S.wg[w];
-      bj = S.wj[w];
-    }
-  }
-  g_best = bg;
-  j_best = bj < m ? bj : 0;   // no column won (every g NaN): still an index inside the problem
+  const ArgBest best = block_argbest<BLOCK, lot_better>(bg, bj, S.wg, S.wj);
+  return ArgBest{best.v, best.j < m ? best.j : 0};   // no column won (every g NaN): column 0
 }
 
 template <int BLOCK, bool STAGED>
@@ -168,9 +140,7 @@ __global__ __launch_bounds__(BLOCK) void nash_lottery_kernel(
   double f_prev = wave_sum_bcast(lane < A ? log(S.a[lane]) : 0.0, width);
   int32_t iters = 0;
   for (int32_t it = 0; it < max_iters; ++it) {
-    double g_best;
-    int32_t jstar;
-    lot_gradient_argmax<BLOCK, STAGED>(S, Ug, smU, A, m, ldu, g_best, jstar);
+    const int32_t jstar = lot_gradient_argmax<BLOCK, STAGED>(S, Ug, smU, A, m, ldu).j;
     if (tid < 64) {
       const bool on = lane < A;
       const double a = on ? S.a[lane] : 1.0;
@@ -234,27 +204,10 @@ __global__ __launch_bounds__(BLOCK) void nash_lottery_kernel(
     if (tid == 0) out_F[prob] = f;
   }
   if (out_gap) {
-    double g_best;
-    int32_t jstar;
-    lot_gradient_argmax<BLOCK, STAGED>(S, Ug, smU, A, m, ldu, g_best, jstar);
+    const double g_best = lot_gradient_argmax<BLOCK, STAGED>(S, Ug, smU, A, m, ldu).v;
     if (tid == 0) out_gap[prob] = g_best - static_cast<double>(A);
   }
   if (out_iters && tid == 0) out_iters[prob] = iters;
-}
-
-template <int BLOCK, bool STAGED>
-void launch_lottery(hipStream_t st, int32_t P, size_t lds, const double* U, int32_t A, int32_t m,
-                    int64_t ldu, int64_t ldp, int32_t max_iters, double tol, double* out_p,
-                    double* out_a, double* out_F, double* out_gap, int32_t* out_iters) {
-  if (STAGED && lds > 64 * 1024) {
-    // more dynamic LDS than the default launch limit: raised once per process
-    static const hipError_t raised = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&nash_lottery_kernel<BLOCK, STAGED>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLotLdsBytes));
-    (void)raised;  // a refusal shows as the launch's own error
-  }
-  hipLaunchKernelGGL((nash_lottery_kernel<BLOCK, STAGED>), dim3(P), dim3(BLOCK), lds, st, U, A, m, ldu,
-                     ldp, max_iters, tol, out_p, out_a, out_F, out_gap, out_iters);
 }
 
 // ---------------------------------------------------------------------------
@@ -351,37 +304,39 @@ __device__ __forceinline__ bool mmx_better(double g, int32_t j, double g0, int32
   return g < g0 || (g == g0 && j < j0);
 }
 
+// M[l][j] of the coalition in S: read from LDS when STAGED, else U divided by base at the read
+template <bool STAGED>
+struct MmxM {
+  const MmxSmem& S;
+  const double *smM, *Ug;
+  int64_t ldu;
+  int32_t m;
+  __device__ __forceinline__ double operator()(int32_t l, int32_t j) const {
+    return STAGED ? smM[static_cast<int64_t>(l) * m + j] : Ug[S.agent[l] * ldu + j] / S.bs[l];
+  }
+};
+
+__device__ __forceinline__ bool mmx_is_basic(const MmxSmem& S, int32_t j) {
+  return (S.basic[j >> 5] >> (j & 31)) & 1u;
+}
+
+// Setup: the coalition's agents and bases into S, the problem's entries checked (all A rows),
+// the coalition's rows of M checked and staged into smM.  Returns (block-uniform) whether the
+// problem has no answer: an empty coalition, a bad base or entry, a member's row of M all zero.
 template <int BLOCK, bool STAGED>
-__global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
-    const double* __restrict__ U, int32_t A, int32_t m, int64_t ldu, int64_t ldp,
-    const double* __restrict__ base, const unsigned long long* __restrict__ masks, int32_t C,
-    int32_t max_pivots, double* __restrict__ out_alpha, double* __restrict__ out_q,
-    double* __restrict__ out_lambda, int32_t* __restrict__ out_pivots) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  __shared__ MmxSmem S;
+__device__ __forceinline__ int mmx_setup(MmxSmem& S, const double* Ug, int32_t A, int32_t m,
+                                         int64_t ldu, const double* base, unsigned long long mask,
+                                         int32_t r, double* smM) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t prob = blockIdx.x / C;
-  const int32_t coal = blockIdx.x % C;
-  const double* Ug = U + prob * ldp;
-  const int64_t slot = prob * C + coal;
-
-  const unsigned long long all = A == 64 ? ~0ull : (1ull << A) - 1ull;
-  const unsigned long long mask = (masks ? masks[coal] : all) & all;
-  const int32_t r = __popcll(mask);
-  const int32_t ldb = r | 1;      // odd row stride: a column of Binv spreads over the banks
-  double* Binv = sm;
-  const double* smM = sm + static_cast<int64_t>(A) * (A | 1);   // where the host put M's share
-
   int bad = r == 0;
   if (tid < 64 && ((mask >> tid) & 1ull)) {
     const int32_t l = __popcll(mask & ((1ull << tid) - 1ull));
-    const double b = base ? base[prob * A + tid] : 1.0;
+    const double b = base ? base[tid] : 1.0;
     S.agent[l] = tid;
     S.bs[l] = b;
     if (!(b > 0.0 && b < INFINITY)) bad = 1;
   }
   __syncthreads();
-  // the problem's entries checked (all A rows), the coalition's rows of M checked and staged
   unsigned long long pos = 0;
   for (int32_t j = tid; j < m; j += BLOCK) {
     for (int32_t i = 0; i < A; ++i) {
@@ -392,7 +347,7 @@ __global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
       const double v = Ug[S.agent[l] * ldu + j] / S.bs[l];
       if (v > 0.0) pos |= 1ull << l;
       if (v == INFINITY) bad = 1;          // U / base overflowed
-      if (STAGED) sm[static_cast<int64_t>(A) * (A | 1) + static_cast<int64_t>(l) * m + j] = v;
+      if (STAGED) smM[static_cast<int64_t>(l) * m + j] = v;
     }
   }
   for (int k = 1; k < 64; k <<= 1) pos |= __shfl_xor(pos, k, 64);
@@ -400,168 +355,137 @@ __global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
   bad = __syncthreads_or(bad);
   for (int w = 0; w < BLOCK / 64; ++w) pos |= S.wpos[w];
   const unsigned long long rows = r == 64 ? ~0ull : (1ull << r) - 1ull;
-  if (pos != rows) bad = 1;                // a member whose row of M is all zero (block-uniform)
+  if (pos != rows) bad = 1;                // a member whose row of M is all zero
+  return bad;
+}
 
-  auto M = [&](int32_t l, int32_t j) -> double {
-    return STAGED ? smM[static_cast<int64_t>(l) * m + j] : Ug[S.agent[l] * ldu + j] / S.bs[l];
-  };
-  auto is_basic = [&](int32_t j) -> bool { return (S.basic[j >> 5] >> (j & 31)) & 1u; };
-
-  int32_t status = bad ? -1 : 0;           // block-uniform from here on
-  if (!bad && m == 1) {
-    // one column: q = (1), value = min_l M[l][0], the weight on the lowest row that attains it
-    if (tid == 0) {
-      int32_t kmin = 0;
-      double vmin = M(0, 0);
-      for (int32_t l = 1; l < r; ++l) {
-        const double v = M(l, 0);
-        if (v < vmin) {
-          vmin = v;
-          kmin = l;
-        }
-      }
-      out_alpha[slot] = (static_cast<double>(r) / static_cast<double>(A)) * vmin;
-      if (out_q) out_q[slot] = 1.0;
-      if (out_lambda)
-        for (int32_t i = 0; i < A; ++i) out_lambda[slot * A + i] = i == S.agent[kmin] ? 1.0 : 0.0;
-      out_pivots[slot] = 0;
-    }
-    return;
-  }
-  if (!bad) {
-    for (int32_t idx = tid; idx < r * r; idx += BLOCK) {
-      const int32_t i = idx / r, l = idx - i * r;
-      Binv[i * ldb + l] = i == l ? 1.0 : 0.0;
-    }
-    if (tid < r) {
-      S.xB[tid] = -1.0;
-      S.w[tid] = 0.0;
-      S.basis[tid] = m + tid;
-    }
-    for (int32_t wi = tid; wi < (m + r + 31) / 32; wi += BLOCK) {
-      uint32_t v = 0;
-      for (int b = 0; b < 32; ++b) {
-        const int32_t j = wi * 32 + b;
-        if (j >= m && j < m + r) v |= 1u << b;
-      }
-      S.basic[wi] = v;
-    }
-    int32_t pivots = 0;
-    for (;;) {
-      __syncthreads();
-      int32_t k = 0;
-      double xk = S.xB[0];
-      for (int32_t i = 1; i < r; ++i) {
-        const double x = S.xB[i];
-        if (x < xk) {
-          xk = x;
-          k = i;
-        }
-      }
-      if (!(xk < 0.0)) {
-        status = pivots;
-        break;
-      }
-      if (pivots >= max_pivots) {
-        status = -2;
-        break;
-      }
-      // the ratio test over this thread's columns
-      const double* rho = Binv + k * ldb;
-      double bg = INFINITY;
-      int32_t bj = 0x7fffffff;
-      for (int32_t j = tid; j < m + r; j += BLOCK) {
-        if (is_basic(j)) continue;
-        double a, d;
-        if (j < m) {
-          double acc_a = 0.0, acc_d = 0.0;
-          for (int32_t l = 0; l < r; ++l) {
-            const double v = M(l, j);
-            acc_a += rho[l] * v;
-            acc_d += S.w[l] * v;
-          }
-          a = -acc_a;
-          d = fmax(1.0 - acc_d, 0.0);
-        } else {
-          a = rho[j - m];
-          d = S.w[j - m];
-        }
-        if (a < 0.0) {
-          const double g = d / -a;
-          if (mmx_better(g, j, bg, bj)) {
-            bg = g;
-            bj = j;
-          }
-        }
-      }
-      for (int s = 1; s < 64; s <<= 1) {
-        const double og = shfl_xor_f64(bg, s);
-        const int32_t oj = __shfl_xor(bj, s, 64);
-        if (mmx_better(og, oj, bg, bj)) {
-          bg = og;
-          bj = oj;
-        }
-      }
-      if (lane == 0) {
-        S.wg[wave] = bg;
-        S.wj[wave] = bj;
-      }
-      __syncthreads();
-      bg = S.wg[0];
-      bj = S.wj[0];
-      for (int w = 1; w < BLOCK / 64; ++w) {
-        if (mmx_better(S.wg[w], S.wj[w], bg, bj)) {
-          bg = S.wg[w];
-          bj = S.wj[w];
-        }
-      }
-      const int32_t e = bj;
-      if (e >= m + r) {                    // no column can enter: rounding only, the LP is feasible
-        status = -2;
-        break;
-      }
-      // the entering column in the basis' coordinates, the new pivot row, the step
-      double theta = 0.0, de = 0.0;
-      if (tid < r) {
-        double ti, piv;
-        if (e < m) {
-          double acc_t = 0.0, acc_p = 0.0, acc_d = 0.0;
-          for (int32_t l = 0; l < r; ++l) {
-            const double v = M(l, e);
-            acc_t += Binv[tid * ldb + l] * -v;
-            acc_p += rho[l] * -v;
-            acc_d += S.w[l] * v;
-          }
-          ti = acc_t;
-          piv = acc_p;
-          de = fmax(1.0 - acc_d, 0.0);
-        } else {
-          ti = Binv[tid * ldb + (e - m)];
-          piv = rho[e - m];
-          de = S.w[e - m];
-        }
-        theta = xk / piv;
-        S.t[tid] = ti;
-        S.row[tid] = rho[tid] / piv;
-      }
-      __syncthreads();
-      for (int32_t idx = tid; idx < r * r; idx += BLOCK) {
-        const int32_t i = idx / r, l = idx - i * r;
-        Binv[i * ldb + l] = i == k ? S.row[l] : Binv[i * ldb + l] - S.t[i] * S.row[l];
-      }
-      if (tid < r) {
-        S.xB[tid] = tid == k ? theta : S.xB[tid] - S.t[tid] * theta;
-        S.w[tid] = fmax(S.w[tid] - de * S.row[tid], 0.0);
-      }
-      if (tid == 0) {
-        const int32_t out = S.basis[k];
-        S.basic[out >> 5] &= ~(1u << (out & 31));
-        S.basic[e >> 5] |= 1u << (e & 31);
-        S.basis[k] = e;
-      }
-      ++pivots;
+// Step 1: the most negative xB and its row (the lowest row on ties) as (v, j)
+__device__ __forceinline__ ArgBest mmx_leaving_row(const MmxSmem& S, int32_t r) {
+  int32_t k = 0;
+  double xk = S.xB[0];
+  for (int32_t i = 1; i < r; ++i) {
+    const double x = S.xB[i];
+    if (x < xk) {
+      xk = x;
+      k = i;
     }
   }
+  return ArgBest{xk, k};
+}
+
+// Step 2: the entering column, the block's best ratio d_j / -a_j over the nonbasic columns with
+// a_j < 0 against the pivot row rho = Binv[k]; >= m + r when no column can enter
+template <int BLOCK, bool STAGED>
+__device__ __forceinline__ int32_t mmx_ratio_test(MmxSmem& S, const MmxM<STAGED>& M,
+                                                  const double* rho, int32_t r, int32_t m) {
+  double bg = INFINITY;
+  int32_t bj = 0x7fffffff;
+  for (int32_t j = threadIdx.x; j < m + r; j += BLOCK) {
+    if (mmx_is_basic(S, j)) continue;
+    double a, d;
+    if (j < m) {
+      double acc_a = 0.0, acc_d = 0.0;
+      for (int32_t l = 0; l < r; ++l) {
+        const double v = M(l, j);
+        acc_a += rho[l] * v;
+        acc_d += S.w[l] * v;
+      }
+      a = -acc_a;
+      d = fmax(1.0 - acc_d, 0.0);
+    } else {
+      a = rho[j - m];
+      d = S.w[j - m];
+    }
+    if (a < 0.0) {
+      const double g = d / -a;
+      if (mmx_better(g, j, bg, bj)) {
+        bg = g;
+        bj = j;
+      }
+    }
+  }
+  return block_argbest<BLOCK, mmx_better>(bg, bj, S.wg, S.wj).j;
+}
+
+// Steps 3 and 4: thread i < r forms t[i], the new pivot row and the step for the entering column
+// e, then Binv, xB and w are eliminated and thread 0 moves the basis
+template <int BLOCK, bool STAGED>
+__device__ __forceinline__ void mmx_pivot(MmxSmem& S, const MmxM<STAGED>& M, double* Binv,
+                                          int32_t ldb, int32_t k, double xk, int32_t e, int32_t r,
+                                          int32_t m) {
+  const int tid = threadIdx.x;
+  const double* rho = Binv + k * ldb;
+  double theta = 0.0, de = 0.0;
+  if (tid < r) {
+    double ti, piv;
+    if (e < m) {
+      double acc_t = 0.0, acc_p = 0.0, acc_d = 0.0;
+      for (int32_t l = 0; l < r; ++l) {
+        const double v = M(l, e);
+        acc_t += Binv[tid * ldb + l] * -v;
+        acc_p += rho[l] * -v;
+        acc_d += S.w[l] * v;
+      }
+      ti = acc_t;
+      piv = acc_p;
+      de = fmax(1.0 - acc_d, 0.0);
+    } else {
+      ti = Binv[tid * ldb + (e - m)];
+      piv = rho[e - m];
+      de = S.w[e - m];
+    }
+    theta = xk / piv;
+    S.t[tid] = ti;
+    S.row[tid] = rho[tid] / piv;
+  }
+  __syncthreads();
+  for (int32_t idx = tid; idx < r * r; idx += BLOCK) {
+    const int32_t i = idx / r, l = idx - i * r;
+    Binv[i * ldb + l] = i == k ? S.row[l] : Binv[i * ldb + l] - S.t[i] * S.row[l];
+  }
+  if (tid < r) {
+    S.xB[tid] = tid == k ? theta : S.xB[tid] - S.t[tid] * theta;
+    S.w[tid] = fmax(S.w[tid] - de * S.row[tid], 0.0);
+  }
+  if (tid == 0) {
+    const int32_t out = S.basis[k];
+    S.basic[out >> 5] &= ~(1u << (out & 31));
+    S.basic[e >> 5] |= 1u << (e & 31);
+    S.basis[k] = e;
+  }
+}
+
+// A one-column problem: q = (1), value = min_l M[l][0], the weight on the lowest such row
+template <bool STAGED>
+__device__ __forceinline__ void mmx_write_one_column(const MmxSmem& S, const MmxM<STAGED>& M,
+                                                     int32_t A, int32_t r, int64_t slot,
+                                                     double* out_alpha, double* out_q,
+                                                     double* out_lambda, int32_t* out_pivots) {
+  if (threadIdx.x != 0) return;
+  int32_t kmin = 0;
+  double vmin = M(0, 0);
+  for (int32_t l = 1; l < r; ++l) {
+    const double v = M(l, 0);
+    if (v < vmin) {
+      vmin = v;
+      kmin = l;
+    }
+  }
+  out_alpha[slot] = (static_cast<double>(r) / static_cast<double>(A)) * vmin;
+  if (out_q) out_q[slot] = 1.0;
+  if (out_lambda)
+    for (int32_t i = 0; i < A; ++i) out_lambda[slot * A + i] = i == S.agent[kmin] ? 1.0 : 0.0;
+  out_pivots[slot] = 0;
+}
+
+// The answer of a solve that ended with `status` (block-uniform): q = x / 1.x, lambda = w / 1.w
+// and alpha from the optimal basis, or NaN and the negative status
+template <int BLOCK>
+__device__ __forceinline__ void mmx_write_out(MmxSmem& S, int32_t status, unsigned long long mask,
+                                              int32_t A, int32_t r, int32_t m, int64_t slot,
+                                              double* out_alpha, double* out_q, double* out_lambda,
+                                              int32_t* out_pivots) {
+  const int tid = threadIdx.x;
   if (status >= 0) {
     if (tid == 0) {
       double sx = 0.0, sw = 0.0;
@@ -589,7 +513,7 @@ __global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
   if (out_q) {
     for (int32_t j = tid; j < m; j += BLOCK) {
       double q = 0.0;
-      if (is_basic(j))
+      if (mmx_is_basic(S, j))
         for (int32_t i = 0; i < r; ++i)
           if (S.basis[i] == j) q = S.xB[i] / sx;
       out_q[slot * m + j] = q;
@@ -607,21 +531,78 @@ __global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
 }
 
 template <int BLOCK, bool STAGED>
-void launch_maximin(hipStream_t st, int64_t grid, size_t lds, const double* U, int32_t A, int32_t m,
-                    int64_t ldu, int64_t ldp, const double* base, const uint64_t* masks, int32_t C,
-                    int32_t max_pivots, double* out_alpha, double* out_q, double* out_lambda,
-                    int32_t* out_pivots) {
-  if (lds > 64 * 1024) {
-    // more dynamic LDS than the default launch limit: raised once per process
-    static const hipError_t raised = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&maximin_lottery_kernel<BLOCK, STAGED>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLotLdsBytes));
-    (void)raised;  // a refusal shows as the launch's own error
+__global__ __launch_bounds__(BLOCK) void maximin_lottery_kernel(
+    const double* __restrict__ U, int32_t A, int32_t m, int64_t ldu, int64_t ldp,
+    const double* __restrict__ base, const unsigned long long* __restrict__ masks, int32_t C,
+    int32_t max_pivots, double* __restrict__ out_alpha, double* __restrict__ out_q,
+    double* __restrict__ out_lambda, int32_t* __restrict__ out_pivots) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ MmxSmem S;
+  const int tid = threadIdx.x;
+  const int64_t prob = blockIdx.x / C;
+  const int32_t coal = blockIdx.x % C;
+  const double* Ug = U + prob * ldp;
+  const int64_t slot = prob * C + coal;
+
+  const unsigned long long all = A == 64 ? ~0ull : (1ull << A) - 1ull;
+  const unsigned long long mask = (masks ? masks[coal] : all) & all;
+  const int32_t r = __popcll(mask);
+  const int32_t ldb = r | 1;      // odd row stride: a column of Binv spreads over the banks
+  double* Binv = sm;
+  double* smM = sm + static_cast<int64_t>(A) * (A | 1);   // where the host put M's share
+  const MmxM<STAGED> M{S, smM, Ug, ldu, m};
+
+  const int bad =
+      mmx_setup<BLOCK, STAGED>(S, Ug, A, m, ldu, base ? base + prob * A : nullptr, mask, r, smM);
+  int32_t status = bad ? -1 : 0;           // block-uniform from here on
+  if (!bad && m == 1) {
+    mmx_write_one_column(S, M, A, r, slot, out_alpha, out_q, out_lambda, out_pivots);
+    return;
   }
-  hipLaunchKernelGGL((maximin_lottery_kernel<BLOCK, STAGED>), dim3(static_cast<uint32_t>(grid)),
-                     dim3(BLOCK), lds, st, U, A, m, ldu, ldp, base,
-                     reinterpret_cast<const unsigned long long*>(masks), C, max_pivots, out_alpha,
-                     out_q, out_lambda, out_pivots);
+  if (!bad) {
+    // the all-slack basis: Binv = I, xB = -1, w = 0, the slacks m .. m + r - 1 basic (inline:
+    // as a function of its own it costs the one-wave kernel six VGPRs and a wave of occupancy)
+    for (int32_t idx = tid; idx < r * r; idx += BLOCK) {
+      const int32_t i = idx / r, l = idx - i * r;
+      Binv[i * ldb + l] = i == l ? 1.0 : 0.0;
+    }
+    if (tid < r) {
+      S.xB[tid] = -1.0;
+      S.w[tid] = 0.0;
+      S.basis[tid] = m + tid;
+    }
+    for (int32_t wi = tid; wi < (m + r + 31) / 32; wi += BLOCK) {
+      uint32_t v = 0;
+      for (int b = 0; b < 32; ++b) {
+        const int32_t j = wi * 32 + b;
+        if (j >= m && j < m + r) v |= 1u << b;
+      }
+      S.basic[wi] = v;
+    }
+    int32_t pivots = 0;
+    for (;;) {
+      __syncthreads();
+      const ArgBest out = mmx_leaving_row(S, r);
+      const int32_t k = out.j;
+      const double xk = out.v;
+      if (!(xk < 0.0)) {
+        status = pivots;
+        break;
+      }
+      if (pivots >= max_pivots) {
+        status = -2;
+        break;
+      }
+      const int32_t e = mmx_ratio_test<BLOCK, STAGED>(S, M, Binv + k * ldb, r, m);
+      if (e >= m + r) {                    // no column can enter: rounding only, the LP is feasible
+        status = -2;
+        break;
+      }
+      mmx_pivot<BLOCK, STAGED>(S, M, Binv, ldb, k, xk, e, r, m);
+      ++pivots;
+    }
+  }
+  mmx_write_out<BLOCK>(S, status, mask, A, r, m, slot, out_alpha, out_q, out_lambda, out_pivots);
 }
 
 // ---------------------------------------------------------------------------
@@ -762,6 +743,41 @@ int64_t pow_limited(int32_t B, int32_t L, int64_t limit) {
   return n;
 }
 
+// Argument checks (w: the entry point's name as the messages' prefix): the P problems [A, m] of
+// the two solvers
+int check_problems(const std::string& w, int32_t P, int32_t A, int32_t m, int64_t ldu, int64_t ldp) {
+  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
+  if (A < 1 || A > kLotMaxA) return fail(CS_ERR_INVALID, w + "need 1 <= A <= 64");
+  if (m < 1 || m > kLotMaxM) return fail(CS_ERR_INVALID, w + "need 1 <= m <= 16384");
+  if (ldu < m) return fail(CS_ERR_INVALID, w + "need ldu >= m");
+  if (ldp < static_cast<int64_t>(A - 1) * ldu + m)
+    return fail(CS_ERR_INVALID, w + "problems overlap (need ldp_problem >= (A - 1) * ldu + m)");
+  return CS_OK;
+}
+
+// the P token trees of B actions and depth L; m = B^L leaves, total = sum_t B^t entries (t = 1..L)
+int check_trees(const std::string& w, int32_t P, int32_t B, int32_t L, int64_t& m, int64_t& total) {
+  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
+  if (B < 1 || L < 1) return fail(CS_ERR_INVALID, w + "need B >= 1 and L >= 1");
+  if (L > kPolicyMaxL) return fail(CS_ERR_INVALID, w + "need L <= 64");
+  m = pow_limited(B, L, kLotMaxM);
+  if (m < 0) return fail(CS_ERR_INVALID, w + "need B^L <= 16384");
+  total = 0;
+  for (int64_t t = 1, n = B; t <= L; ++t, n *= B) total += n;
+  return CS_OK;
+}
+
+// f(block, staged): BLOCK (1024 when wide, else 256) and STAGED as integral_constant values
+template <typename F>
+void dispatch_block_staged(bool wide, bool staged, F&& f) {
+  auto go = [&](auto block) {
+    if (staged) f(block, std::true_type{});
+    else f(block, std::false_type{});
+  };
+  if (wide) go(std::integral_constant<int, 1024>{});
+  else go(std::integral_constant<int, 256>{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -771,12 +787,7 @@ int cs_nash_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ld
                     double* out_a, double* out_F, double* out_gap, int32_t* out_iters,
                     cs_stream_t stream) {
   const std::string w = "cs_nash_lottery: ";
-  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
-  if (A < 1 || A > kLotMaxA) return fail(CS_ERR_INVALID, w + "need 1 <= A <= 64");
-  if (m < 1 || m > kLotMaxM) return fail(CS_ERR_INVALID, w + "need 1 <= m <= 16384");
-  if (ldu < m) return fail(CS_ERR_INVALID, w + "need ldu >= m");
-  if (ldp_problem < static_cast<int64_t>(A - 1) * ldu + m)
-    return fail(CS_ERR_INVALID, w + "problems overlap (need ldp_problem >= (A - 1) * ldu + m)");
+  if (int rc = check_problems(w, P, A, m, ldu, ldp_problem)) return rc;
   if (max_iters < 0) return fail(CS_ERR_INVALID, w + "need max_iters >= 0");
   if (!std::isfinite(tol)) return fail(CS_ERR_INVALID, w + "tol must be finite");
   if (variant < 0 || variant > 2) return fail(CS_ERR_INVALID, w + "unknown variant");
@@ -785,26 +796,18 @@ int cs_nash_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t ld
     return fail(CS_ERR_INVALID, w + "variant 1 needs A * m * 8 bytes of LDS, at most 147456");
   if (P == 0) return CS_OK;
   if (!U || !out_p) return fail(CS_ERR_INVALID, w + "NULL pointer");
-  if (reinterpret_cast<uintptr_t>(U) % 8 != 0 || reinterpret_cast<uintptr_t>(out_p) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(out_a) % 8 != 0 || reinterpret_cast<uintptr_t>(out_F) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(out_gap) % 8 != 0 || reinterpret_cast<uintptr_t>(out_iters) % 4 != 0)
+  if (misaligned(U, 8) || misaligned(out_p, 8) || misaligned(out_a, 8) || misaligned(out_F, 8) ||
+      misaligned(out_gap, 8) || misaligned(out_iters, 4))
     return fail(CS_ERR_INVALID, w + "U and the fp64 outputs must be 8-byte aligned");
   // variant 0: staged whenever U fits ("The Nash-welfare lottery")
   const bool staged = variant == 1 || (variant == 0 && u_bytes <= kLotLdsBytes);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  auto go = [&](auto block, auto stg) {
-    launch_lottery<decltype(block)::value, decltype(stg)::value>(
-        st, P, decltype(stg)::value ? u_bytes : 0, U, A, m, ldu, ldp_problem, max_iters, tol, out_p,
-        out_a, out_F, out_gap, out_iters);
-  };
-  using std::integral_constant;
-  if (m > kLotWideM) {
-    if (staged) go(integral_constant<int, 1024>{}, std::true_type{});
-    else go(integral_constant<int, 1024>{}, std::false_type{});
-  } else {
-    if (staged) go(integral_constant<int, 256>{}, std::true_type{});
-    else go(integral_constant<int, 256>{}, std::false_type{});
-  }
+  dispatch_block_staged(m > kLotWideM, staged, [&](auto block, auto stg) {
+    constexpr int BLOCK = decltype(block)::value;
+    constexpr bool STAGED = decltype(stg)::value;
+    launch_big_lds<&nash_lottery_kernel<BLOCK, STAGED>>(
+        kLotLdsBytes, dim3(P), dim3(BLOCK), STAGED ? u_bytes : 0, static_cast<hipStream_t>(stream),
+        U, A, m, ldu, ldp_problem, max_iters, tol, out_p, out_a, out_F, out_gap, out_iters);
+  });
   return check_launch("cs_nash_lottery");
 }
 
@@ -813,12 +816,7 @@ int cs_maximin_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t
                        const uint64_t* masks, int32_t C, int32_t max_pivots, double* out_alpha,
                        double* out_q, double* out_lambda, int32_t* out_pivots, cs_stream_t stream) {
   const std::string w = "cs_maximin_lottery: ";
-  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
-  if (A < 1 || A > kLotMaxA) return fail(CS_ERR_INVALID, w + "need 1 <= A <= 64");
-  if (m < 1 || m > kLotMaxM) return fail(CS_ERR_INVALID, w + "need 1 <= m <= 16384");
-  if (ldu < m) return fail(CS_ERR_INVALID, w + "need ldu >= m");
-  if (ldp_problem < static_cast<int64_t>(A - 1) * ldu + m)
-    return fail(CS_ERR_INVALID, w + "problems overlap (need ldp_problem >= (A - 1) * ldu + m)");
+  if (int rc = check_problems(w, P, A, m, ldu, ldp_problem)) return rc;
   if (max_pivots < 0) return fail(CS_ERR_INVALID, w + "need max_pivots >= 0");
   if (C < 1) return fail(CS_ERR_INVALID, w + "need C >= 1");
   if ((masks_host == nullptr) != (masks == nullptr))
@@ -835,51 +833,37 @@ int cs_maximin_lottery(const double* U, int32_t P, int32_t A, int32_t m, int64_t
   if (int rc = check_grid("cs_maximin_lottery", grid)) return rc;
   if (P == 0) return CS_OK;
   if (!U || !out_alpha || !out_pivots) return fail(CS_ERR_INVALID, w + "NULL pointer");
-  if (reinterpret_cast<uintptr_t>(U) % 8 != 0 || reinterpret_cast<uintptr_t>(base) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(masks) % 8 != 0 || reinterpret_cast<uintptr_t>(out_alpha) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(out_q) % 8 != 0 || reinterpret_cast<uintptr_t>(out_lambda) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(out_pivots) % 4 != 0)
+  if (misaligned(U, 8) || misaligned(base, 8) || misaligned(masks, 8) || misaligned(out_alpha, 8) ||
+      misaligned(out_q, 8) || misaligned(out_lambda, 8) || misaligned(out_pivots, 4))
     return fail(CS_ERR_INVALID, w + "U, base, masks and the fp64 outputs must be 8-byte aligned");
   // Binv's share is sized by A (a coalition has at most A rows); M is staged whenever it fits too
   const size_t binv_bytes = static_cast<size_t>(A) * (A | 1) * sizeof(double);
   const size_t m_bytes = static_cast<size_t>(A) * m * sizeof(double);
   const bool staged = binv_bytes + m_bytes <= kLotLdsBytes;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   auto go = [&](auto block, auto stg) {
-    launch_maximin<decltype(block)::value, decltype(stg)::value>(
-        st, grid, binv_bytes + (decltype(stg)::value ? m_bytes : 0), U, A, m, ldu, ldp_problem, base,
-        masks, C, max_pivots, out_alpha, out_q, out_lambda, out_pivots);
+    constexpr int BLOCK = decltype(block)::value;
+    constexpr bool STAGED = decltype(stg)::value;
+    launch_big_lds<&maximin_lottery_kernel<BLOCK, STAGED>>(
+        kLotLdsBytes, dim3(static_cast<uint32_t>(grid)), dim3(BLOCK),
+        binv_bytes + (STAGED ? m_bytes : 0), static_cast<hipStream_t>(stream), U, A, m, ldu,
+        ldp_problem, base, reinterpret_cast<const unsigned long long*>(masks), C, max_pivots,
+        out_alpha, out_q, out_lambda, out_pivots);
   };
-  using std::integral_constant;
-  if (m <= kMmxNarrowM) {
-    go(integral_constant<int, 64>{}, std::true_type{});   // 64 x 65 + 64 x 128 doubles always fit
-  } else if (m <= kLotWideM) {
-    if (staged) go(integral_constant<int, 256>{}, std::true_type{});
-    else go(integral_constant<int, 256>{}, std::false_type{});
-  } else {
-    if (staged) go(integral_constant<int, 1024>{}, std::true_type{});
-    else go(integral_constant<int, 1024>{}, std::false_type{});
-  }
+  // one wave per workgroup up to kMmxNarrowM columns: 64 x 65 + 64 x 128 doubles always fit
+  if (m <= kMmxNarrowM) go(std::integral_constant<int, 64>{}, std::true_type{});
+  else dispatch_block_staged(m > kLotWideM, staged, go);
   return check_launch("cs_maximin_lottery");
 }
 
 int cs_lottery_policy(const double* p, int32_t P, int32_t B, int32_t L, double* out_policy,
                       cs_stream_t stream) {
   const std::string w = "cs_lottery_policy: ";
-  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
-  if (B < 1 || L < 1) return fail(CS_ERR_INVALID, w + "need B >= 1 and L >= 1");
-  if (L > kPolicyMaxL) return fail(CS_ERR_INVALID, w + "need L <= 64");
-  const int64_t m = pow_limited(B, L, kLotMaxM);
-  if (m < 0) return fail(CS_ERR_INVALID, w + "need B^L <= 16384");
+  int64_t m, total;
+  if (int rc = check_trees(w, P, B, L, m, total)) return rc;
   if (P == 0) return CS_OK;
   if (!p || !out_policy) return fail(CS_ERR_INVALID, w + "NULL pointer");
-  if (reinterpret_cast<uintptr_t>(p) % 8 != 0 || reinterpret_cast<uintptr_t>(out_policy) % 8 != 0)
+  if (misaligned(p, 8) || misaligned(out_policy, 8))
     return fail(CS_ERR_INVALID, w + "p and out_policy must be 8-byte aligned");
-  int64_t total = 0, n = 1;
-  for (int32_t t = 1; t <= L; ++t) {
-    n *= B;
-    total += n;
-  }
   hipLaunchKernelGGL(lottery_policy_kernel, dim3(P), dim3(kPolicyBlock), 0,
                      static_cast<hipStream_t>(stream), p, B, L, static_cast<int32_t>(m),
                      static_cast<int32_t>(total), out_policy);
@@ -891,11 +875,8 @@ int cs_policy_rollout(const double* policy, int32_t P, int32_t B, int32_t L, con
                       int64_t* out_counts, int32_t* out_leaf, int32_t* out_status,
                       cs_stream_t stream) {
   const std::string w = "cs_policy_rollout: ";
-  if (P < 0) return fail(CS_ERR_INVALID, w + "need P >= 0");
-  if (B < 1 || L < 1) return fail(CS_ERR_INVALID, w + "need B >= 1 and L >= 1");
-  if (L > kPolicyMaxL) return fail(CS_ERR_INVALID, w + "need L <= 64");
-  const int64_t m = pow_limited(B, L, kLotMaxM);
-  if (m < 0) return fail(CS_ERR_INVALID, w + "need B^L <= 16384");
+  int64_t m, total;
+  if (int rc = check_trees(w, P, B, L, m, total)) return rc;
   if (first_sample < 0 || num_samples < 0)
     return fail(CS_ERR_INVALID, w + "need first_sample >= 0 and num_samples >= 0");
   const u128 draws = (static_cast<u128>(first_sample) + static_cast<u128>(num_samples)) * L;
@@ -903,22 +884,15 @@ int cs_policy_rollout(const double* policy, int32_t P, int32_t B, int32_t L, con
     return fail(CS_ERR_INVALID, w + "need (first_sample + num_samples) * L < 2^62");
   if (out_leaf && static_cast<u128>(P) * static_cast<u128>(num_samples) > 0x7fffffffu)
     return fail(CS_ERR_INVALID, w + "out_leaf needs P * num_samples <= 2^31 - 1");
-  const int64_t chunks = (num_samples + kRollPerGroup - 1) / kRollPerGroup;
+  const int64_t chunks = cdiv(num_samples, kRollPerGroup);
   if (chunks > 0x7fffffffLL) return fail(CS_ERR_INVALID, w + "grid too large");
   if (int rc = check_grid("cs_policy_rollout", static_cast<int64_t>(P) * chunks)) return rc;
   if (P == 0 || num_samples == 0) return CS_OK;
   if (!policy || !rng || !cdf_work || !out_counts || !out_status)
     return fail(CS_ERR_INVALID, w + "NULL pointer");
-  if (reinterpret_cast<uintptr_t>(policy) % 8 != 0 || reinterpret_cast<uintptr_t>(rng) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(cdf_work) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(out_counts) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(out_leaf) % 4 != 0 || reinterpret_cast<uintptr_t>(out_status) % 4 != 0)
+  if (misaligned(policy, 8) || misaligned(rng, 8) || misaligned(cdf_work, 8) ||
+      misaligned(out_counts, 8) || misaligned(out_leaf, 4) || misaligned(out_status, 4))
     return fail(CS_ERR_INVALID, w + "policy, rng, cdf_work and out_counts must be 8-byte aligned");
-  int64_t total = 0, n = 1;
-  for (int32_t t = 1; t <= L; ++t) {
-    n *= B;
-    total += n;
-  }
   const int32_t rows = static_cast<int32_t>(total / B);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(rollout_cdf_kernel, dim3(P), dim3(kRollBlock), 0, st, policy, B, rows, cdf_work,

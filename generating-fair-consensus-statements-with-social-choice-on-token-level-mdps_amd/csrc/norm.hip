@@ -16,27 +16,10 @@
 
 namespace {
 
-typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf(uint16_t v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
 
 constexpr int kNormThreads = 256;
 constexpr int kMaxSplits = 16;      // K-split partials folded by cs_add_rms_norm_splitk
-
-// the row's sum over the workgroup: wave64 butterfly, then the BLOCK / 64 wave sums in wave
-// order (the same order everywhere, so a norm is bitwise the same in every kernel that uses it)
-template <int BLOCK = kNormThreads>
-__device__ __forceinline__ float row_sum(float ss, float* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  float tot = 0.0f;
-#pragma unroll
-  for (int i = 0; i < BLOCK / 64; ++i) tot += red[i];
-  return tot;
-}
 
 // one workgroup per row; VPT 16-byte vectors per thread (d <= 256 * 8 * VPT).  s_out may
 // alias a (the residual stream updated in place): every element is loaded before the
@@ -126,7 +109,7 @@ __global__ __launch_bounds__(BLOCK) void add_rms_kernel(
         for (int e = 0; e < 8; ++e) sb = fmaf(bf(bv[k][e]), bf(bv[k][e]), sb);
       }
     }
-    const float inv_b = 1.0f / sqrtf(row_sum<BLOCK>(sb, red[0]) / static_cast<float>(d) + eps);
+    const float inv_b = 1.0f / sqrtf(block_sum<BLOCK>(sb, red[0]) / static_cast<float>(d) + eps);
 #pragma unroll
     for (int k = 0; k < VPT; ++k) {
       const int v = threadIdx.x + k * BLOCK;
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(BLOCK) void add_rms_kernel(
       for (int e = 0; e < 8; ++e) ss = fmaf(bf(av[k][e]), bf(av[k][e]), ss);
     }
   }
-  const float inv = 1.0f / sqrtf(row_sum<BLOCK>(ss, red[1]) / static_cast<float>(d) + eps);
+  const float inv = 1.0f / sqrtf(block_sum<BLOCK>(ss, red[1]) / static_cast<float>(d) + eps);
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = threadIdx.x + k * BLOCK;
@@ -273,7 +256,7 @@ int cs_add_rms_norm_splitk(const void* a, int64_t lda, const float* partials, in
                            cs_stream_t stream) {
   if (!partials || splits < 1 || splits > kMaxSplits)
     return fail(CS_ERR_INVALID, "cs_add_rms_norm_splitk: partials and 1 <= splits <= 16 required");
-  if (reinterpret_cast<uintptr_t>(partials) & 15)
+  if (misaligned(partials, 16))
     return fail(CS_ERR_INVALID, "cs_add_rms_norm_splitk: partials must be 16-byte aligned");
   return add_rms_launch("cs_add_rms_norm_splitk", a, lda, nullptr, 0, partials, splits, b_weight,
                         s_out, lds, weight, rows, d, eps, plus_one, y, ldy, stream);
@@ -287,7 +270,7 @@ int cs_gated_act(const void* gate, int64_t ld_gate, const void* up, int64_t ld_u
   if (act != 0 && act != 1) return fail(CS_ERR_INVALID, "cs_gated_act: act must be 0 (SiLU) or 1 (tanh-GeLU)");
   if (F % 8 || ld_gate % 8 || ld_up % 8 || ld_out % 8 || ld_gate < F || ld_up < F || ld_out < F)
     return fail(CS_ERR_INVALID, "cs_gated_act: F and leading dimensions must be multiples of 8, >= F");
-  const int64_t nb = (F / 8 + kNormThreads - 1) / kNormThreads;
+  const int64_t nb = cdiv(F / 8, kNormThreads);
   if (rows * nb > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_gated_act: grid too large");
   hipLaunchKernelGGL(gated_act_kernel, dim3(static_cast<uint32_t>(rows * nb)), dim3(kNormThreads), 0,
                      static_cast<hipStream_t>(stream), static_cast<const uint16_t*>(gate), ld_gate,

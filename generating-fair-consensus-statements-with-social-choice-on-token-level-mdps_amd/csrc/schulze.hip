@@ -273,23 +273,6 @@ __global__ __launch_bounds__(BLOCK) void schulze_kernel(
   }
 }
 
-template <int BLOCK>
-void launch_schulze(hipStream_t st, int32_t E, size_t lds, const void* in, int kind, int32_t R,
-                    int32_t C, const uint8_t* valid, const int32_t* ballot, int32_t* out_defeats,
-                    int32_t* out_strengths, int32_t* out_ranking, int32_t* out_untied,
-                    int32_t* out_winner, int32_t* out_status) {
-  if (lds > 64 * 1024) {
-    // more dynamic LDS than the default launch limit: raised once per process
-    static const hipError_t raised = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&schulze_kernel<BLOCK>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kSchLdsMax));
-    (void)raised;  // a refusal shows as the launch's own error
-  }
-  hipLaunchKernelGGL((schulze_kernel<BLOCK>), dim3(static_cast<uint32_t>(E)), dim3(BLOCK), lds, st,
-                     in, kind, R, C, valid, ballot, out_defeats, out_strengths, out_ranking,
-                     out_untied, out_winner, out_status);
-}
-
 }  // namespace
 
 extern "C" {
@@ -309,13 +292,9 @@ int cs_schulze(const void* in, int in_kind, int32_t E, int32_t R, int32_t C, con
   if (int rc = check_grid("cs_schulze", E)) return rc;
   if (E == 0) return CS_OK;
   if (!in || !out_ranking || !out_status) return fail(CS_ERR_INVALID, w + "NULL pointer");
-  if (reinterpret_cast<uintptr_t>(in) % 4 != 0 || reinterpret_cast<uintptr_t>(ballot) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(out_defeats) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(out_strengths) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(out_ranking) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(out_untied) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(out_winner) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(out_status) % 4 != 0)
+  if (misaligned(in, 4) || misaligned(ballot, 4) || misaligned(out_defeats, 4) ||
+      misaligned(out_strengths, 4) || misaligned(out_ranking, 4) || misaligned(out_untied, 4) ||
+      misaligned(out_winner, 4) || misaligned(out_status, 4))
     return fail(CS_ERR_INVALID, w + "in, ballot and the outputs must be 4-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t lds = sch_lds_bytes(C);
@@ -323,12 +302,15 @@ int cs_schulze(const void* in, int in_kind, int32_t E, int32_t R, int32_t C, con
     R = 0;
     valid = nullptr;
   }
-  if (C <= kSchNarrowC)
-    launch_schulze<64>(st, E, lds, in, in_kind, R, C, valid, ballot, out_defeats, out_strengths,
-                       out_ranking, out_untied, out_winner, out_status);
-  else
-    launch_schulze<256>(st, E, lds, in, in_kind, R, C, valid, ballot, out_defeats, out_strengths,
-                        out_ranking, out_untied, out_winner, out_status);
+  auto go = [&](auto block) {
+    constexpr int BLOCK = decltype(block)::value;
+    launch_big_lds<&schulze_kernel<BLOCK>>(kSchLdsMax, dim3(static_cast<uint32_t>(E)), dim3(BLOCK),
+                                           lds, st, in, in_kind, R, C, valid, ballot, out_defeats,
+                                           out_strengths, out_ranking, out_untied, out_winner,
+                                           out_status);
+  };
+  if (C <= kSchNarrowC) go(std::integral_constant<int, 64>{});
+  else go(std::integral_constant<int, 256>{});
   return check_launch("cs_schulze");
 }
 

@@ -96,9 +96,7 @@ def _bad_rank_message(rankings: np.ndarray) -> str:
 
 # --- the launches ---------------------------------------------------------------------------
 def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise ops.CSError("Schulze aggregation runs on the GPU (cs_schulze); there is no CPU path")
-    return torch.device("cuda", torch.cuda.current_device())
+    return ops.default_device("Schulze aggregation runs on the GPU (cs_schulze); there is no CPU path")
 
 
 def _check_limits(R: Optional[int], C: int) -> None:

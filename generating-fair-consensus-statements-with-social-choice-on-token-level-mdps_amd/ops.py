@@ -40,6 +40,18 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """The tensor's address; None or an empty tensor gives NULL."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def default_device(who: str) -> torch.device:
+    """The current HIP device; without one, CSError(who): there is no CPU path."""
+    if not torch.cuda.is_available():
+        raise CSError(who)
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 def _require_cuda(*ts: torch.Tensor) -> None:
     dev = None
     for t in ts:
@@ -1125,6 +1137,19 @@ def rows_from_blocked(vt: torch.Tensor) -> torch.Tensor:
     return vt.transpose(-1, -2).reshape(*lead, nb * w, D)
 
 
+def _problem_args(U: torch.Tensor, *others: Optional[torch.Tensor]):
+    """The solvers' problems U [A, m] or [P, A, m] as (batched, P, A, m, ldu, ldp, device)."""
+    if U.dim() not in (2, 3) or U.dtype != torch.float64 or (U.stride(-1) != 1 and U.shape[-1] > 1):
+        raise CSError("U must be [A, m] or [P, A, m] float64 with unit column stride")
+    _require_cuda(U, *others)
+    batched = U.dim() == 3
+    P = U.shape[0] if batched else 1
+    A, m = U.shape[-2], U.shape[-1]
+    ldu = U.stride(-2) if A > 1 else m
+    ldp = U.stride(0) if batched and P > 1 else max(A, 1) * ldu
+    return batched, P, A, m, ldu, ldp, U.device
+
+
 def nash_lottery(U: torch.Tensor, max_iters: int = 1000, tol: float = 1e-10,
                  variant: int = 0) -> Dict[str, torch.Tensor]:
     """The Nash-welfare lottery of every problem of U in one launch (cs_nash_lottery).
@@ -1136,15 +1161,7 @@ def nash_lottery(U: torch.Tensor, max_iters: int = 1000, tol: float = 1e-10,
     variant: 0 the library's choice, 1 U staged in LDS, 2 U read from global memory (bitwise
     equal outputs).  Restates FW_nash_welfare (core.py:116-168)."""
     L = _lib.load()
-    if U.dim() not in (2, 3) or U.dtype != torch.float64 or (U.stride(-1) != 1 and U.shape[-1] > 1):
-        raise CSError("U must be [A, m] or [P, A, m] float64 with unit column stride")
-    _require_cuda(U)
-    batched = U.dim() == 3
-    P = U.shape[0] if batched else 1
-    A, m = U.shape[-2], U.shape[-1]
-    ldu = U.stride(-2) if A > 1 else m
-    ldp = U.stride(0) if batched and P > 1 else max(A, 1) * ldu
-    dev = U.device
+    batched, P, A, m, ldu, ldp, dev = _problem_args(U)
     p = torch.empty((P, m), dtype=torch.float64, device=dev)
     a = torch.empty((P, A), dtype=torch.float64, device=dev)
     F = torch.empty(P, dtype=torch.float64, device=dev)
@@ -1205,15 +1222,7 @@ def maximin_lottery(U: torch.Tensor, base: Optional[torch.Tensor] = None, masks=
     exhausted.  with_q / with_lam = False leave that output out.
     Restates the LPs of egalitarian_lottery and max_coalition_improvement (core.py:171-279)."""
     L = _lib.load()
-    if U.dim() not in (2, 3) or U.dtype != torch.float64 or (U.stride(-1) != 1 and U.shape[-1] > 1):
-        raise CSError("U must be [A, m] or [P, A, m] float64 with unit column stride")
-    _require_cuda(U, base)
-    batched = U.dim() == 3
-    P = U.shape[0] if batched else 1
-    A, m = U.shape[-2], U.shape[-1]
-    ldu = U.stride(-2) if A > 1 else m
-    ldp = U.stride(0) if batched and P > 1 else max(A, 1) * ldu
-    dev = U.device
+    batched, P, A, m, ldu, ldp, dev = _problem_args(U, base)
     if base is not None:
         if base.dtype != torch.float64 or tuple(base.shape) != ((P, A) if batched else (A,)):
             raise CSError("base must be float64 of shape [A] (or [P, A] for batched U)")
@@ -1227,10 +1236,9 @@ def maximin_lottery(U: torch.Tensor, base: Optional[torch.Tensor] = None, masks=
     q = torch.empty((P, C, m), dtype=torch.float64, device=dev) if with_q else None
     lam = torch.empty((P, C, A), dtype=torch.float64, device=dev) if with_lam else None
     pivots = torch.empty((P, C), dtype=torch.int32, device=dev)
-    rc = L.cs_maximin_lottery(U.data_ptr(), P, A, m, ldu, ldp,
-                              None if base is None else base.data_ptr(), mh, md, C, int(max_pivots),
-                              alpha.data_ptr(), None if q is None else q.data_ptr(),
-                              None if lam is None else lam.data_ptr(), pivots.data_ptr(), _stream())
+    rc = L.cs_maximin_lottery(U.data_ptr(), P, A, m, ldu, ldp, _ptr(base), mh, md, C,
+                              int(max_pivots), alpha.data_ptr(), _ptr(q), _ptr(lam),
+                              pivots.data_ptr(), _stream())
     _lib.check(rc, "cs_maximin_lottery")
     out = {"alpha": alpha, "pivots": pivots}
     if with_q:
@@ -1240,6 +1248,12 @@ def maximin_lottery(U: torch.Tensor, base: Optional[torch.Tensor] = None, masks=
     if masks is None:
         out = {k: v[:, 0] for k, v in out.items()}
     return out if batched else {k: v[0] for k, v in out.items()}
+
+
+def _tree_sizes(B: int, L: int) -> list:
+    """A token tree's level sizes B^(t+1); [0] for a shape the entry points reject (unallocated)."""
+    sizes = [B ** (t + 1) for t in range(L)] if 1 <= B and 1 <= L <= 64 else [0]
+    return sizes if sizes[-1] <= 16384 else [0]
 
 
 def lottery_policy(p: torch.Tensor, B: int, L: int, *, flat: bool = False):
@@ -1256,9 +1270,7 @@ def lottery_policy(p: torch.Tensor, B: int, L: int, *, flat: bool = False):
     _require_cuda(p)
     batched = p.dim() == 2
     P = p.shape[0] if batched else 1
-    sizes = [B ** (t + 1) for t in range(L)] if 1 <= B and 1 <= L <= 64 else [0]
-    if sizes[-1] > 16384:
-        sizes = [0]          # the entry point rejects the shape; nothing that large is allocated
+    sizes = _tree_sizes(B, L)
     if sizes[-1] and p.shape[-1] != sizes[-1]:
         raise CSError(f"p has {p.shape[-1]} leaves, B^L is {sizes[-1]}")
     out = torch.empty((P, sum(sizes)), dtype=torch.float64, device=p.device)
@@ -1339,9 +1351,7 @@ def policy_rollout(policy, B: int, L: int, rng_state, num_samples: int, first_sa
     policy = policy.contiguous()
     batched = policy.dim() == 2
     P = policy.shape[0] if batched else 1
-    sizes = [B ** (t + 1) for t in range(L)] if 1 <= B and 1 <= L <= 64 else [0]
-    if sizes[-1] > 16384:
-        sizes = [0]          # the entry point rejects the shape; nothing that large is allocated
+    sizes = _tree_sizes(B, L)
     m = sizes[-1]
     if m and policy.shape[-1] != sum(sizes):
         raise CSError(f"policy has {policy.shape[-1]} entries per problem, "
@@ -1361,14 +1371,22 @@ def policy_rollout(policy, B: int, L: int, rng_state, num_samples: int, first_sa
     if with_leaves:      # -1: the leaves of a problem of status -1 stay untouched
         leaves = torch.full((P, max(num_samples, 0)), -1, dtype=torch.int32, device=dev)
     rc = L_.cs_policy_rollout(policy.data_ptr(), P, B, L, rng.data_ptr(), first_sample, num_samples,
-                              work.data_ptr(), counts.data_ptr(),
-                              leaves.data_ptr() if leaves is not None and leaves.numel() else None,
-                              status.data_ptr(), _stream())
+                              work.data_ptr(), counts.data_ptr(), _ptr(leaves), status.data_ptr(),
+                              _stream())
     _lib.check(rc, "cs_policy_rollout")
     out = {"counts": counts, "status": status if batched else status[0]}
     if with_leaves:
         out["leaves"] = leaves if batched else leaves[0]
     return out
+
+
+def _valid_u8(v: Optional[torch.Tensor], shape: tuple, name: str, dims: Optional[str] = None):
+    """An optional bool / uint8 mask of ``shape`` as uint8; ``dims`` spells it in the message."""
+    if v is None:
+        return None
+    if v.dtype not in (torch.bool, torch.uint8) or tuple(v.shape) != tuple(shape):
+        raise CSError(f"{name} must be a bool or uint8 {dims or list(shape)} tensor")
+    return v.to(torch.uint8).contiguous()
 
 
 SCHULZE_KINDS = {"rankings": _lib.SCHULZE_RANKINGS, "scores": _lib.SCHULZE_SCORES,
@@ -1412,10 +1430,7 @@ def schulze(x: torch.Tensor, kind: str = "rankings", valid: Optional[torch.Tenso
     x = x.contiguous()
     E, R, C = x.shape
     dev = x.device
-    if valid is not None:
-        if valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (E, R):
-            raise CSError("valid must be a bool or uint8 [E, R] tensor")
-        valid = valid.to(torch.uint8).contiguous()
+    valid = _valid_u8(valid, (E, R), "valid", "[E, R]")
     if ballot is not None:
         if ballot.dtype != torch.int32 or tuple(ballot.shape) != (E, C):
             raise CSError("ballot must be an int32 [E, C] tensor")
@@ -1428,9 +1443,8 @@ def schulze(x: torch.Tensor, kind: str = "rankings", valid: Optional[torch.Tenso
     strengths = new(E, C, C) if k != _lib.SCHULZE_STRENGTHS and with_strengths else None
     ranking, winner, status = new(E, C), new(E), new(E)
     untied = new(E, C) if ballot is not None else None
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731
-    rc = L.cs_schulze(x.data_ptr(), k, E, R, C, ptr(valid), ptr(ballot), ptr(defeats),
-                      ptr(strengths), ranking.data_ptr(), ptr(untied), winner.data_ptr(),
+    rc = L.cs_schulze(x.data_ptr(), k, E, R, C, _ptr(valid), _ptr(ballot), _ptr(defeats),
+                      _ptr(strengths), ranking.data_ptr(), _ptr(untied), winner.data_ptr(),
                       status.data_ptr(), _stream())
     _lib.check(rc, "cs_schulze")
     out = {"ranking": ranking, "winner": winner, "status": status}
@@ -1444,6 +1458,16 @@ def schulze(x: torch.Tensor, kind: str = "rankings", valid: Optional[torch.Tenso
 def _vec_bf16(t: torch.Tensor, d: int, name: str) -> None:
     if t.dtype != torch.bfloat16 or t.numel() != d or not t.is_contiguous():
         raise CSError(f"{name} must be a contiguous bfloat16 [{d}] tensor")
+
+
+def _out_like(out: Optional[torch.Tensor], shape: tuple, device: torch.device, what: str):
+    """(out, row stride): a fresh bf16 ``shape`` when None, else bf16 rows of it or CSError(what)."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=device)
+    ld = _rows2d(out, "out")
+    if tuple(out.shape) != tuple(shape):
+        raise CSError(what)
+    return out, ld
 
 
 def _ragged_args(cu_seqlens: torch.Tensor, n_tok: int, max_seqlen: int):
@@ -1482,11 +1506,7 @@ def embed_layer_norm(ids: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: in
         status = torch.zeros(1, dtype=torch.int32, device=ids.device)
     elif status.dtype != torch.int32 or status.numel() != 1:
         raise CSError("status must be an int32 [1] tensor")
-    if out is None:
-        out = torch.empty(n_tok, d, dtype=torch.bfloat16, device=ids.device)
-    ldy = _rows2d(out, "out")
-    if tuple(out.shape) != (n_tok, d):
-        raise CSError("out must be [n_tok, d]")
+    out, ldy = _out_like(out, (n_tok, d), ids.device, "out must be [n_tok, d]")
     _require_cuda(ids, cu_seqlens, word_emb, pos_emb, type_emb, weight, bias, status, out)
     rc = L.cs_embed_layer_norm(ids.data_ptr(), cu_seqlens.data_ptr(), n_text, n_tok, int(max_seqlen),
                                word_emb.data_ptr(), int(word_emb.shape[0]), pos_emb.data_ptr(),
@@ -1512,15 +1532,10 @@ def add_layer_norm(x: torch.Tensor, residual: Optional[torch.Tensor], weight: to
         raise CSError("x and residual must share one shape")
     _vec_bf16(weight, d, "weight")
     _vec_bf16(bias, d, "bias")
-    if out is None:
-        out = torch.empty(rows, d, dtype=torch.bfloat16, device=x.device)
-    ldy = _rows2d(out, "out")
-    if out.shape != x.shape:
-        raise CSError("out must have x's shape")
+    out, ldy = _out_like(out, (rows, d), x.device, "out must have x's shape")
     _require_cuda(x, residual, weight, bias, out)
-    rc = L.cs_add_layer_norm(x.data_ptr(), ldx, residual.data_ptr() if residual is not None else None,
-                             ldr, weight.data_ptr(), bias.data_ptr(), rows, d, float(eps),
-                             out.data_ptr(), ldy, _stream())
+    rc = L.cs_add_layer_norm(x.data_ptr(), ldx, _ptr(residual), ldr, weight.data_ptr(),
+                             bias.data_ptr(), rows, d, float(eps), out.data_ptr(), ldy, _stream())
     _lib.check(rc, "cs_add_layer_norm")
     return out
 
@@ -1530,11 +1545,7 @@ def gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     L = _lib.load()
     ldx = _rows2d(x, "x")
     rows, F = x.shape
-    if out is None:
-        out = torch.empty(rows, F, dtype=torch.bfloat16, device=x.device)
-    ldy = _rows2d(out, "out")
-    if out.shape != x.shape:
-        raise CSError("out must have x's shape")
+    out, ldy = _out_like(out, (rows, F), x.device, "out must have x's shape")
     _require_cuda(x, out)
     rc = L.cs_gelu(x.data_ptr(), ldx, rows, F, out.data_ptr(), ldy, _stream())
     _lib.check(rc, "cs_gelu")
@@ -1583,22 +1594,13 @@ def cosine_welfare(E_s: torch.Tensor, E_a: torch.Tensor, valid_s: Optional[torch
     A = E_a.shape[0]
     if E_a.shape[1] != d:
         raise CSError("E_s and E_a must share the embedding width")
-
-    def vb(v, n, name):
-        if v is None:
-            return None
-        if v.dtype not in (torch.bool, torch.uint8) or tuple(v.shape) != (n,):
-            raise CSError(f"{name} must be a bool or uint8 [{n}] tensor")
-        return v.to(torch.uint8).contiguous()
-
-    valid_s, valid_a = vb(valid_s, S, "valid_s"), vb(valid_a, A, "valid_a")
+    valid_s, valid_a = _valid_u8(valid_s, (S,), "valid_s"), _valid_u8(valid_a, (A,), "valid_a")
     _require_cuda(E_s, E_a, valid_s, valid_a)
     cos = torch.empty(A, S, dtype=torch.float64, device=E_s.device)
     wel = torch.empty(3, S, dtype=torch.float64, device=E_s.device)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731
-    rc = L.cs_cosine_welfare(ptr(E_s), E_s.stride(0) if S > 1 else d, ptr(E_a),
-                             E_a.stride(0) if A > 1 else d, ptr(valid_s), ptr(valid_a), S, A, d,
-                             float(eps), ptr(cos), ptr(wel), _stream())
+    rc = L.cs_cosine_welfare(_ptr(E_s), E_s.stride(0) if S > 1 else d, _ptr(E_a),
+                             E_a.stride(0) if A > 1 else d, _ptr(valid_s), _ptr(valid_a), S, A, d,
+                             float(eps), _ptr(cos), _ptr(wel), _stream())
     _lib.check(rc, "cs_cosine_welfare")
     return cos, wel
 

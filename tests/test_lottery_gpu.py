@@ -104,7 +104,8 @@ def test_certificate_is_recomputed_from_p(core, ops, dev, golden):
 
 
 # 3 ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("A,m", [(6, 81), (1, 1), (1, 2), (64, 100), (16, 1000)])
+@pytest.mark.parametrize("A,m", [(6, 81), (1, 1), (1, 2), (64, 100), (16, 1000),
+                                 (2, 4097)])   # m > 4096: the 1024-thread launch, 16 waves
 def test_variants_are_bitwise_equal(ops, dev, A, m):
     U = _cuda(_rand_u(100 * A + m, A, m, 2.0), dev)
     r1 = ops.nash_lottery(U, max_iters=100, variant=1)
@@ -124,6 +125,7 @@ def test_variants_are_bitwise_equal(ops, dev, A, m):
     (16, 4096, 0),              # 512 KiB of utilities: the library's choice is the global path
     (1, 10, 0), (63, 50, 0), (64, 50, 0),
     (6, 81, 3),                 # ldu = m + 3
+    (2, 4097, 0),               # m > 4096: the 1024-thread launch
 ])
 def test_shapes_against_restatement(ops, dev, A, m, pad):
     tol = 1e-10
@@ -172,6 +174,22 @@ def test_ties_take_the_lowest_index(ops, dev):
     _check_against(res, ref, "duplicate column")
     # columns 40 and `top` only ever decay, with the columns that are never chosen
     assert res["p"][40] == res["p"].min() == res["p"][top] and res["p"][40] < res["p"][5]
+    # m > 4096, the 1024-thread launch: the best column of the first iteration copied to columns
+    # 5 and 1000, which threads of the first and the last of the 16 waves hold; the first vertex
+    # is the lower index, so after one iteration every other column still has (1 - gamma) / m
+    U = _rand_u(5, 6, 4097)
+    g = (U / U.mean(axis=1)[:, None]).sum(axis=0)
+    top = int(np.argmax(g))
+    assert top > 5
+    U[:, 5] = U[:, top]
+    U[:, 1000] = U[:, top]
+    g = (U / U.mean(axis=1)[:, None]).sum(axis=0)
+    assert g[5] == g[1000] == g.max() and np.sort(g)[-4] < g.max() - 1.0   # a clear margin
+    ref = lottery_ref.solve(U, max_iters=1)
+    res = _np(ops.nash_lottery(_cuda(U, dev), max_iters=1))
+    _check_against(res, ref, "duplicate column, 16 waves")
+    assert int(np.argmax(res["p"])) == 5 and res["p"][5] > 0.1
+    assert res["p"][1000] == res["p"].min() == res["p"][top]
 
 
 def test_all_equal_utilities_and_zero_iterations(ops, dev):
