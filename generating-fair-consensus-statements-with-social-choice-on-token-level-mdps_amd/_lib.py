@@ -39,6 +39,8 @@ EXPORTED = (
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
     "cs_maximin_lottery", "cs_policy_rollout", "cs_schulze",
     "cs_sample_step_workspace_size", "cs_sample_step",
+    "cs_vocab_sample_ex_workspace_size", "cs_vocab_sample_ex",
+    "cs_sample_step_ex_workspace_size", "cs_sample_step_ex",
     "cs_embed_layer_norm", "cs_add_layer_norm", "cs_gelu", "cs_encoder_attention",
     "cs_cosine_welfare",
     "cs_standardize_workspace_size", "cs_standardize", "cs_kmeans_workspace_size",
@@ -177,6 +179,17 @@ def load():
     L.cs_sample_step.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, vp, vp, i32, f32, vp,
                                  i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     L.cs_sample_step.restype = ctypes.c_int
+    L.cs_vocab_sample_ex_workspace_size.argtypes = [i64, i64, i32]
+    L.cs_vocab_sample_ex_workspace_size.restype = ctypes.c_size_t
+    L.cs_vocab_sample_ex.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, i32, vp, i32, f32,
+                                     f32, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.cs_vocab_sample_ex.restype = ctypes.c_int
+    L.cs_sample_step_ex_workspace_size.argtypes = [i64, i64]
+    L.cs_sample_step_ex_workspace_size.restype = ctypes.c_size_t
+    L.cs_sample_step_ex.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, vp, vp, i32, f32,
+                                    f32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp,
+                                    vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.cs_sample_step_ex.restype = ctypes.c_int
     L.cs_embed_layer_norm.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, i32, vp, vp, vp, i64, f32,
                                       vp, i64, vp, vp]
     L.cs_embed_layer_norm.restype = ctypes.c_int

@@ -525,6 +525,133 @@ def sample_step(logits: torch.Tensor, base_seeds: torch.Tensor, step: torch.Tens
     _lib.check(rc, "cs_sample_step")
 
 
+def _id_list(t: Optional[torch.Tensor], name: str):
+    """(pointer or None, count) of an optional 1-D int32 device list."""
+    n = 0 if t is None else t.numel()
+    if n and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+        raise CSError(f"{name} must be a contiguous 1-D int32 tensor")
+    return (t.data_ptr() if n else None), n
+
+
+def _seen_args(seen_ids: Optional[torch.Tensor], seen_off: Optional[torch.Tensor], rows: int):
+    """Pointers of the ragged seen list (both None: no list).  seen_off is int32 [rows + 1]."""
+    if seen_off is None:
+        if seen_ids is not None:
+            raise CSError("seen_ids needs seen_off")
+        return None, None
+    if seen_off.dtype != torch.int32 or tuple(seen_off.shape) != (rows + 1,) \
+            or not seen_off.is_contiguous():
+        raise CSError(f"seen_off must be a contiguous int32 tensor of shape [{rows + 1}]")
+    if seen_ids is None or seen_ids.dtype != torch.int32 or seen_ids.dim() != 1 \
+            or not seen_ids.is_contiguous():
+        raise CSError("seen_ids must be a contiguous 1-D int32 tensor")
+    # an empty tensor's pointer may be NULL: the library wants one whenever offsets are given
+    return (seen_ids.data_ptr() or seen_off.data_ptr()), seen_off.data_ptr()
+
+
+def vocab_sample_ex(logits: torch.Tensor, seeds: Optional[torch.Tensor], *,
+                    temperature: float = 1.0, vocab: Optional[int] = None, softcap: float = 0.0,
+                    bias_ids: Optional[torch.Tensor] = None, bias_value: float = -1e6,
+                    repetition_penalty: float = 1.0, seen_ids: Optional[torch.Tensor] = None,
+                    seen_off: Optional[torch.Tensor] = None, n_draw: Optional[int] = None,
+                    workspace: Optional[Workspace] = None):
+    """``vocab_sample`` with the controls of cs_vocab_sample_ex: bias_ids take bias_value
+    before the soft-cap, the tokens of seen_ids[seen_off[r]:seen_off[r+1]] (int32 device
+    tensors) take the repetition penalty after it, and temperature 0 is greedy (seeds may then
+    be None, with n_draw giving the number of columns, default 1)."""
+    L = _lib.load()
+    rows, ld, vocab = _logits_args(logits, vocab)
+    if seeds is None:
+        n_draw = 1 if n_draw is None else int(n_draw)
+    else:
+        seeds = seeds.reshape(rows, -1)
+        if seeds.dtype != torch.int64 or not seeds.is_contiguous():
+            raise CSError("seeds must be a contiguous int64 tensor [rows, n_draw]")
+        n_draw = seeds.shape[1]
+    _require_cuda(logits, seeds, bias_ids, seen_ids, seen_off)
+    bias_ptr, n_bias = _id_list(bias_ids, "bias_ids")
+    seen_ptr, off_ptr = _seen_args(seen_ids, seen_off, rows)
+    ids = torch.empty((rows, n_draw), dtype=torch.int32, device=logits.device)
+    lp = torch.empty((rows, n_draw), dtype=torch.float32, device=logits.device)
+    _, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _default_ws, int(L.cs_vocab_sample_ex_workspace_size(rows, vocab, n_draw)),
+        logits.device)
+    rc = L.cs_vocab_sample_ex(logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld,
+                              float(temperature), float(softcap),
+                              None if seeds is None else seeds.data_ptr(), n_draw, bias_ptr,
+                              n_bias, float(bias_value), float(repetition_penalty), seen_ptr,
+                              off_ptr, ids.data_ptr(), lp.data_ptr(), ws_ptr, ws_bytes, _stream())
+    _lib.check(rc, "cs_vocab_sample_ex")
+    return ids, lp
+
+
+MAX_STOP_SEQ, MAX_STOP_LEN = 8, 32     # cs_sample_step_ex
+
+
+def sample_step_ex(logits: torch.Tensor, base_seeds: Optional[torch.Tensor], step: torch.Tensor,
+                   done: torch.Tensor, out_len: torch.Tensor, out_tokens: torch.Tensor,
+                   next_tok: torch.Tensor, n_alive: torch.Tensor, *, pad_id: int,
+                   temperature: float = 1.0, softcap: float = 0.0,
+                   bias_ids: Optional[torch.Tensor] = None, bias_value: float = -1e6,
+                   repetition_penalty: float = 1.0, seen_ids: Optional[torch.Tensor] = None,
+                   seen_off: Optional[torch.Tensor] = None,
+                   stop_ids: Optional[torch.Tensor] = None, stop_seqs=(),
+                   tok_bytes: Optional[torch.Tensor] = None,
+                   tok_off: Optional[torch.Tensor] = None, tail: Optional[torch.Tensor] = None,
+                   tail_len: Optional[torch.Tensor] = None,
+                   out_lp: Optional[torch.Tensor] = None, max_tokens: Optional[int] = None,
+                   vocab: Optional[int] = None, workspace: Optional[Workspace] = None) -> None:
+    """``sample_step`` with the controls of cs_sample_step_ex: temperature 0 is greedy, the
+    tokens of seen_ids[seen_off[s]:seen_off[s+1]] and the stream's own out_tokens take the
+    repetition penalty, and stop_seqs (a sequence of bytes objects, held by the host) end a
+    stream whose decoded bytes complete one: tok_bytes (uint8) / tok_off (int32 [vocab + 1])
+    are the tokens' bytes, tail (uint8 [S, 32]) / tail_len (int32 [S]) the per-stream window,
+    zero at the start.  With every control off this is ``sample_step``, bit for bit."""
+    L = _lib.load()
+    S, ld, vocab = _logits_args(logits, vocab)
+    _require_cuda(logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
+                  bias_ids, stop_ids, out_lp, seen_ids, seen_off, tok_bytes, tok_off, tail, tail_len)
+    if max_tokens is None:
+        if out_tokens is None or out_tokens.dim() != 2:
+            raise CSError("out_tokens must be [S, max_tokens] int32")
+        max_tokens = out_tokens.shape[1]
+    max_tokens = int(max_tokens)
+    bias_ptr, n_bias = _id_list(bias_ids, "bias_ids")
+    stop_ptr, n_stop = _id_list(stop_ids, "stop_ids")
+    seen_ptr, off_ptr = _seen_args(seen_ids, seen_off, S)
+    stop_seqs = [bytes(b) for b in stop_seqs]
+    n_seq = len(stop_seqs)
+    offs = [0]
+    for b in stop_seqs:
+        offs.append(offs[-1] + len(b))
+    stop_bytes = ctypes.create_string_buffer(b"".join(stop_seqs), max(1, offs[-1]))
+    stop_off = (ctypes.c_int32 * len(offs))(*offs)
+    dev = logits.device
+    workspace, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _sample_ws, int(L.cs_sample_step_ex_workspace_size(S, vocab)), dev,
+        "sample_step")
+    rc = L.cs_sample_step_ex(
+        logits.data_ptr(), _DTYPE[logits.dtype], S, vocab, ld, float(temperature), float(softcap),
+        _state_ptr(base_seeds, "base_seeds", torch.int64, (S,)),
+        _state_ptr(step, "step", torch.int32, (1,)), bias_ptr, n_bias, float(bias_value),
+        float(repetition_penalty), seen_ptr, off_ptr, stop_ptr, n_stop,
+        _state_ptr(tok_bytes, "tok_bytes", torch.uint8,
+                   tuple(tok_bytes.shape[:1]) if tok_bytes is not None else ()),
+        _state_ptr(tok_off, "tok_off", torch.int32, (vocab + 1,)),
+        ctypes.cast(stop_bytes, ctypes.c_void_p), ctypes.cast(stop_off, ctypes.c_void_p), n_seq,
+        _state_ptr(tail, "tail", torch.uint8, (S, MAX_STOP_LEN)),
+        _state_ptr(tail_len, "tail_len", torch.int32, (S,)), max_tokens, int(pad_id),
+        _state_ptr(done, "done", torch.int32, (S,)),
+        _state_ptr(out_len, "out_len", torch.int32, (S,)),
+        _state_ptr(out_tokens, "out_tokens", torch.int32, (S, max_tokens)),
+        _state_ptr(out_lp, "out_lp", torch.float32, (S, max_tokens)),
+        _state_ptr(next_tok, "next_tok", torch.int64, (S,)),
+        _state_ptr(n_alive, "n_alive", torch.int32, (1,)), ws_ptr, ws_bytes, _stream())
+    if rc != 0:
+        workspace.reset()
+    _lib.check(rc, "cs_sample_step_ex")
+
+
 class AttnPlan:
     """A cs_prefix_attention work plan on the device (entries, counts) and the split
     partials' workspace it needs; built once per (prefix-length bounds, shape) and reused by

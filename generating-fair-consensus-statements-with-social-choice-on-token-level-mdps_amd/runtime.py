@@ -345,15 +345,99 @@ def apply_bias(logits: torch.Tensor, ids: Sequence[int], value: float) -> torch.
     return logits
 
 
+# --- stop strings -------------------------------------------------------------------
+STOP_TAIL = 31      # bytes of decoded text kept between steps (cs_sample_step_ex's window)
+_BARRIER = b"\xff"  # never in UTF-8 text: stands for a token whose text the table lacks
+
+
+def early_stop_strings(stop_strings: Optional[Sequence[str]]) -> List[bytes]:
+    """The stop strings a generation loop may end a stream on BEFORE the caller cuts the
+    text (utils.generate_text: text[:text.find(term)] for each terminator in turn), without
+    changing what that cut returns: ASCII strings of 1 to 32 bytes, at most 8 of them (a
+    byte match in the token bytes is then a match in the decoded text at the same place).
+    None are used if two different strings can overlap in a text with the second ending
+    later (one inside the other, or a suffix of one opening the other): the cut could then
+    find in the longer text an occurrence that the stopped text no longer holds."""
+    if isinstance(stop_strings, str):
+        stop_strings = [stop_strings]
+    terms = [t for t in dict.fromkeys(stop_strings or ()) if t]
+    for a in terms:
+        for b in terms:
+            if a is not b and (b in a or any(a.startswith(b[k:]) for k in range(1, len(b)))):
+                return []
+    ok = [t.encode("ascii") for t in terms if t.isascii() and len(t) <= ops.MAX_STOP_LEN]
+    return ok[:ops.MAX_STOP_SEQ]
+
+
+def stop_token_table(tok, vocab: int) -> Optional[List[bytes]]:
+    """Token id -> bytes for ids [0, vocab) from tok.token_bytes() (None if the tokenizer has
+    no exact table).  A token without bytes there (a special token, an id past the
+    tokenizer's vocabulary) gets one byte no stop string holds, so no match spans it."""
+    tb = tok.token_bytes() if hasattr(tok, "token_bytes") else None
+    if tb is None:
+        return None
+    key = (id(tb), int(vocab))
+    cached = getattr(tok, "_stop_table", None)
+    if cached is None or cached[0] != key:
+        data, off = tb
+        n = len(off) - 1
+        table = [data[off[i]:off[i + 1]] or _BARRIER if i < n else _BARRIER for i in range(vocab)]
+        cached = tok._stop_table = (key, table, {})
+    return cached[1]
+
+
+def _stop_table_device(tok, vocab: int, dev):
+    """(tok_bytes uint8, tok_off int32 [vocab + 1]) of stop_token_table on ``dev``, built
+    once per tokenizer and device."""
+    table = stop_token_table(tok, vocab)
+    if table is None:
+        return None
+    per_dev = tok._stop_table[2]
+    if str(dev) not in per_dev:
+        import numpy as np
+        off = np.zeros(vocab + 1, dtype=np.int32)
+        np.cumsum([len(b) for b in table], out=off[1:])
+        data = np.frombuffer(b"".join(table) + b"\0", dtype=np.uint8).copy()
+        per_dev[str(dev)] = (torch.from_numpy(data).to(dev), torch.from_numpy(off).to(dev))
+    return per_dev[str(dev)]
+
+
+def stop_window_push(tail: bytes, piece: bytes, stops: Sequence[bytes]):
+    """cs_sample_step_ex's window rule on the host: (hit, new tail) after a token with bytes
+    ``piece``; hit if a stop string occurs in tail + piece ending inside piece."""
+    if not piece:
+        return False, tail
+    w = tail + piece
+    hit = any(w.find(s, max(0, len(tail) + 1 - len(s))) != -1 for s in stops)
+    return hit, w[-STOP_TAIL:]
+
+
+def _ragged_i32(lists, dev):
+    """(ids, offsets) int32 device tensors of per-row id lists (ops' seen_ids / seen_off)."""
+    off = [0]
+    for r in lists:
+        off.append(off[-1] + len(r))
+    flat = [int(i) for r in lists for i in r] + [0]          # never an empty allocation
+    return (torch.tensor(flat, dtype=torch.int32, device=dev)[:off[-1]],
+            torch.tensor(off, dtype=torch.int32, device=dev))
+
+
 # --- seeded generation on the engine ------------------------------------------------
 @torch.no_grad()
 def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int],
              seeds: Sequence[Optional[int]], max_tokens: int, temperature: float = 1.0,
              bias_ids: Sequence[int] = (), bias_value: float = -1e6,
-             stop_ids: Optional[Sequence[int]] = None) -> List[List[int]]:
+             stop_ids: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
+             stop_strings: Optional[Sequence[str]] = None) -> List[List[int]]:
     """Sample len(seeds) continuations of one prefix in a batch (token t of stream i
     drawn with seed draw_seed(seeds[i], t)); a stream stops after a stop token (not
-    included) or max_tokens tokens."""
+    included) or max_tokens tokens.
+
+    temperature 0 decodes greedily, repetition_penalty != 1 penalises the prompt's and the
+    stream's own tokens (ops.vocab_sample_ex: the row transform of the device loop), and a
+    stream also ends with the token that completes one of early_stop_strings(stop_strings)
+    (included, so the caller's cut sees it).  With the defaults the draws are
+    ops.vocab_sample's as before."""
     n = len(seeds)
     seeds = [fresh_seed() if s is None else int(s) for s in seeds]
     stop = set(tok.eos_ids if stop_ids is None else stop_ids)
@@ -364,20 +448,40 @@ def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int
     st = BeamState(engine, cache, n_prefix=1)
     alive = list(range(n))          # stream ids, in beam order
     dev = engine.device
+    temperature, penalty = float(temperature), float(repetition_penalty)
+    controls = temperature == 0.0 or penalty != 1.0
+    stops = early_stop_strings(stop_strings)
+    table = stop_token_table(tok, engine.model.cfg.vocab) if stops else None
+    tails = [b""] * n
+    bias_t = torch.tensor(list(bias_ids), dtype=torch.int32, device=dev) \
+        if controls and len(bias_ids) else None
+    prefix_ids = list(prefix_ids)
     for t in range(max_tokens):
         logits = st.next_logits(0).float() if st.n_beams == len(alive) else None
         if st.n_beams == 1 and len(alive) > 1:
             logits = engine.model.lm_head(st.next_hidden).float().expand(len(alive), -1).contiguous()
-        logits = apply_bias(logits, bias_ids, bias_value)
         sd = torch.tensor([[to_i64(draw_seed(seeds[i], t))] for i in alive], dtype=torch.int64,
                           device=dev)
-        ids, _ = ops.vocab_sample(logits, sd, temperature=temperature, softcap=engine.softcap)
+        if controls:
+            seen_ids, seen_off = _ragged_i32([prefix_ids + out[i] for i in alive], dev) \
+                if penalty != 1.0 else (None, None)
+            ids, _ = ops.vocab_sample_ex(logits, sd, temperature=temperature,
+                                         softcap=engine.softcap, bias_ids=bias_t,
+                                         bias_value=float(bias_value), repetition_penalty=penalty,
+                                         seen_ids=seen_ids, seen_off=seen_off)
+        else:
+            logits = apply_bias(logits, bias_ids, bias_value)
+            ids, _ = ops.vocab_sample(logits, sd, temperature=temperature, softcap=engine.softcap)
         ids = ids[:, 0].tolist()
         parent, toks, nxt = [], [], []
         for j, (i, v) in enumerate(zip(alive, ids)):
             if v in stop:
                 continue
             out[i].append(v)
+            if table is not None:
+                hit, tails[i] = stop_window_push(tails[i], table[v], stops)
+                if hit:
+                    continue
             if t + 1 < max_tokens:
                 parent.append(0 if st.n_beams == 1 else j)
                 toks.append(v)
@@ -406,7 +510,9 @@ def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
                      prefixes: Sequence[Sequence[int]], seeds, max_tokens: int,
                      temperature: float = 1.0, bias_ids: Sequence[int] = (),
                      bias_value: float = -1e6, stop_ids: Optional[Sequence[int]] = None,
-                     poll_every: int = 8, return_logprobs: bool = False):
+                     poll_every: int = 8, return_logprobs: bool = False,
+                     repetition_penalty: float = 1.0,
+                     stop_strings: Optional[Sequence[str]] = None):
     """Sample continuations of many prompts at once with the loop closed on the device:
     result[p][i] = the tokens of prompt p under seeds[p][i] (``seeds``: one list used for
     every prompt, or one list per prompt, of any lengths), drawn as ``generate`` draws
@@ -417,7 +523,14 @@ def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
     the LM head and cs_sample_step, which appends the draw and writes the next step's input
     token on the device.  The host reads one word (the number of unfinished streams) every
     ``poll_every`` steps and downloads the tokens once at the end.  bf16 engines only: the
-    stream decode is the bf16 path, and another dtype raises instead of changing numerics."""
+    stream decode is the bf16 path, and another dtype raises instead of changing numerics.
+
+    temperature 0, repetition_penalty and stop_strings are ``generate``'s, applied inside the
+    step (cs_sample_step_ex): each stream's prompt ids are its seen list, which the step
+    extends by the tokens generated so far, and a stream ends with the token whose bytes
+    complete one of early_stop_strings(stop_strings) -- where the tokenizer has an exact
+    token_bytes() table; otherwise the streams run on to a stop token or max_tokens as
+    before.  With the defaults the step is cs_sample_step."""
     from .engine import DecodeState
     P = len(prefixes)
     per = _seed_lists(seeds, P)
@@ -456,14 +569,30 @@ def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
             stop_t = torch.tensor(stop, dtype=torch.int32, device=dev) if stop else None
             pad_id = int(tok.eos_ids[0]) if getattr(tok, "eos_ids", None) else 0
             ws = ops.Workspace(zeroed=True)
+            penalty = float(repetition_penalty)
+            stops = early_stop_strings(stop_strings)
+            tables = _stop_table_device(tok, m.cfg.vocab, dev) if stops else None
+            if tables is None:
+                stops = []
+            ex = {}
+            if float(temperature) == 0.0 or penalty != 1.0 or stops:
+                ex = dict(repetition_penalty=penalty, stop_seqs=stops)
+                if penalty != 1.0:
+                    ex["seen_ids"], ex["seen_off"] = _ragged_i32(
+                        [list(prefixes[p]) for p in range(P) for _ in range(B)], dev)
+                if stops:
+                    ex.update(tok_bytes=tables[0], tok_off=tables[1],
+                              tail=torch.zeros(S, ops.MAX_STOP_LEN, dtype=torch.uint8, device=dev),
+                              tail_len=torch.zeros(S, dtype=torch.int32, device=dev))
+            step_op = ops.sample_step_ex if ex else ops.sample_step
 
             def post():
                 logits = m.lm_head(ds.hidden)                      # [S, V]
-                ops.sample_step(logits, base_t, ds.hist_base, done, out_len, out_tok, ds.tok,
-                                n_alive, pad_id=pad_id, temperature=float(temperature),
-                                softcap=engine.softcap, bias_ids=bias_t,
-                                bias_value=float(bias_value), stop_ids=stop_t, out_lp=out_lp,
-                                workspace=ws)
+                step_op(logits, base_t, ds.hist_base, done, out_len, out_tok, ds.tok,
+                        n_alive, pad_id=pad_id, temperature=float(temperature),
+                        softcap=engine.softcap, bias_ids=bias_t,
+                        bias_value=float(bias_value), stop_ids=stop_t, out_lp=out_lp,
+                        workspace=ws, **ex)
 
             post()                                 # token 0: every stream = its prompt
             every = max(1, int(poll_every))

@@ -38,6 +38,26 @@ UNK = "\ufffd"
 SYNTH_BASE = 0x10000
 
 
+def _pack_bytes(parts: Sequence[bytes]):
+    """(concatenated bytes, offsets [len + 1]) of a list of byte strings."""
+    offsets = [0]
+    for p in parts:
+        offsets.append(offsets[-1] + len(p))
+    return b"".join(parts), offsets
+
+
+def _byte_level_inverse() -> Dict[str, int]:
+    """The inverse of GPT-2's byte-to-unicode map that byte-level BPE vocabularies are
+    spelled in: printable Latin-1 stands for itself, the other bytes for U+0100 onwards."""
+    keep = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+    inv, n = {chr(b): b for b in keep}, 0
+    for b in range(256):
+        if b not in keep:
+            inv[chr(256 + n)] = b
+            n += 1
+    return inv
+
+
 class CharTokenizer:
     """Deterministic char tokenizer: specials, Latin-1, a few extra code points, <unk>.
 
@@ -120,6 +140,19 @@ class CharTokenizer:
 
     def tokens(self, ids: Sequence[int]) -> List[str]:
         return [self.token_str(i) for i in ids]
+
+    def token_bytes(self):
+        """(bytes, offsets) for the whole padded vocabulary: token i's UTF-8 bytes are
+        bytes[offsets[i]:offsets[i + 1]].  Special tokens have no bytes; for every other id
+        sequence the concatenated bytes are decode(ids) in UTF-8.  (The table the device's
+        stop-string test reads, runtime.generate_streams.)"""
+        tb = getattr(self, "_token_bytes", None)
+        if tb is None:
+            n_sp = len(self.special_ids)
+            parts = [b""] * n_sp + [self.token_str(i).encode("utf-8")
+                                    for i in range(n_sp, self.full_vocab)]
+            tb = self._token_bytes = _pack_bytes(parts)
+        return tb
 
     # --- prompt layouts -----------------------------------------------------------
     def render_raw(self, text: str, add_bos: bool = True) -> List[int]:
@@ -271,6 +304,48 @@ class BPETokenizer:
         if all(0 <= i < self.n_table for i in ids):
             return self.tk.decode(ids, skip_special_tokens=False)
         return "".join(self.token_str(i) for i in ids)
+
+    def token_bytes(self):
+        """(bytes, offsets) for the whole padded vocabulary, as CharTokenizer.token_bytes, or
+        None where the table cannot be exact.  It is built for byte-level vocabularies only
+        (token strings spelled in GPT-2's byte-to-unicode alphabet, decoded by a ByteLevel
+        decoder); added tokens have no bytes.  Checked once on seeded random id sequences:
+        their concatenated bytes, decoded as UTF-8 with replacement, must equal decode(ids) --
+        a wrong table would cut text, a missing one only costs decode steps."""
+        if not hasattr(self, "_token_bytes"):
+            self._token_bytes = self._build_token_bytes()
+        return self._token_bytes
+
+    def _build_token_bytes(self):
+        import json
+        import random
+
+        try:
+            dec = json.loads(self.tk.to_str()).get("decoder") or {}
+        except Exception:
+            return None
+        kinds = [dec.get("type")] + [d.get("type") for d in dec.get("decoders", [])]
+        if kinds != ["ByteLevel"]:
+            return None
+        inv = _byte_level_inverse()
+        added = set(self.tk.get_added_tokens_decoder())
+        parts = [b""] * self.full_vocab
+        for s, i in self.tk.get_vocab(with_added_tokens=True).items():
+            if i in added or not 0 <= i < self.n_table:
+                continue
+            try:
+                parts[i] = bytes(inv[c] for c in s)
+            except KeyError:
+                return None
+        for i in range(self.n_table, self.full_vocab):
+            parts[i] = chr(SYNTH_BASE + i).encode("utf-8")
+        plain = [i for i in range(self.n_table) if i not in added and parts[i]]
+        rng = random.Random(0)
+        for _ in range(64 if plain else 0):
+            ids = [rng.choice(plain) for _ in range(rng.randint(1, 24))]
+            if b"".join(parts[i] for i in ids).decode("utf-8", errors="replace") != self.decode(ids):
+                return None
+        return _pack_bytes(parts)
 
     def append_stable(self, prefix_text: str, prefix_ids: Sequence[int], piece: str,
                       piece_ids: Sequence[int]) -> bool:

@@ -598,7 +598,10 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
 
     Chat mode renders the chat template with the generation prompt; completions mode
     uses the raw ``system + "\\n\\n" + user`` prompt.  Token t is drawn with seed
-    draw_seed(seed, t); stop tokens end the text and are not included."""
+    draw_seed(seed, t); stop tokens end the text and are not included.  temperature 0
+    decodes greedily, repetition_penalty is transformers' rule over the prompt's and the
+    generated tokens, and a terminator ends the decoding where it can (runtime.generate);
+    the cut below decides the returned text in every case."""
     try:
         engine, tok = runtime.get_engine(model)
         if use_chat_completions:
@@ -609,7 +612,9 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
         bias = runtime.bias_token_ids(tok, bias_against_tokens)
         with runtime.device_lock(engine.device):
             out = runtime.generate(engine, tok, ids, [seed], max_tokens, float(temperature),
-                                   bias_ids=bias, bias_value=float(bias_value))[0]
+                                   bias_ids=bias, bias_value=float(bias_value),
+                                   repetition_penalty=float(repetition_penalty),
+                                   stop_strings=terminators)[0]
         text = tok.decode(out)
         for term in terminators or ():
             cut = text.find(term)
@@ -623,7 +628,8 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
 
 def generate_texts(model, user_prompts, system_prompts=None, n_per_prompt=1, max_tokens=4096,
                    temperature=1, terminators=(), seeds=None, bias_against_tokens=None,
-                   bias_value=-1000000, use_chat_completions=True) -> List[List[str]]:
+                   bias_value=-1000000, use_chat_completions=True,
+                   repetition_penalty=1.0) -> List[List[str]]:
     """The batch form of generate_text: result[p][i] = completion i of prompt p, every prompt
     and sample decoded together on the device (runtime.generate_streams; bf16 engines).
 
@@ -660,7 +666,9 @@ def generate_texts(model, user_prompts, system_prompts=None, n_per_prompt=1, max
         bias = runtime.bias_token_ids(tok, bias_against_tokens)
         outs = runtime.generate_streams(engine, tok, idss, [None] * n if seeds is None else seeds,
                                         max_tokens, float(temperature), bias_ids=bias,
-                                        bias_value=float(bias_value))
+                                        bias_value=float(bias_value),
+                                        repetition_penalty=float(repetition_penalty),
+                                        stop_strings=terminators)
         texts = []
         for row in outs:
             texts.append([])

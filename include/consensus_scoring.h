@@ -308,6 +308,80 @@ int cs_sample_step(const void* logits, int dtype, int64_t S, int64_t vocab, int6
                    cs_stream_t stream);
 
 /*
+ * cs_vocab_sample_ex — cs_vocab_sample with a logit bias, a repetition penalty and greedy
+ * decoding, all inside the one pass over the row.
+ *
+ * The row that is drawn from, in fp32, for token v of row r:
+ *   x = float(logits[r][v]) + (v listed in bias_ids ? bias_value : 0), then the soft-cap
+ *     (cs_sample_step's biased row: once per token however often listed, ids outside
+ *     [0, vocab) ignored);
+ *   if repetition_penalty != 1 and v is in seen_ids[seen_off[r] : seen_off[r+1]] (int32,
+ *     device, seen_off [rows + 1]; both NULL: no list): x = x < 0 ? x * penalty : x / penalty,
+ *     a correctly rounded fp32 division: transformers' RepetitionPenaltyLogitsProcessor on the
+ *     model's final logits, before the temperature.  Ids outside [0, vocab) are ignored,
+ *     duplicates count once, -inf stays -inf and NaN stays NaN.
+ * temperature > 0: cs_vocab_sample's Gumbel-max draws on x / temperature.
+ * temperature == 0: greedy.  Every draw is the argmax of x, ties to the lowest id; seeds is
+ *   not read (may be NULL); out_lp is the token's log-probability under softmax(x).
+ * The never-drawn and poisoned-row rules of cs_vocab_sample hold on x.
+ * With temperature > 0, no bias and no penalty (penalty 1 or no list) the call IS
+ * cs_vocab_sample: same kernels, same bits.
+ * Limits: those of cs_vocab_sample, n_bias <= 1024, penalty finite and > 0, and at most 2^19
+ * tokens per row slice (two LDS bitmaps over the slice).
+ */
+size_t cs_vocab_sample_ex_workspace_size(int64_t rows, int64_t vocab, int32_t n_draw);
+int cs_vocab_sample_ex(const void* logits, int dtype, int64_t rows, int64_t vocab, int64_t ld,
+                       float temperature, float softcap, const uint64_t* seeds, int32_t n_draw,
+                       const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                       float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                       int32_t* out_ids, float* out_lp, void* workspace, size_t workspace_bytes,
+                       cs_stream_t stream);
+
+/*
+ * cs_sample_step_ex — cs_sample_step with greedy decoding, a repetition penalty and stop
+ * strings; still two launches, and still replayable from a captured graph with no new
+ * argument.
+ *
+ * For an unfinished stream s, id and lp are bit for bit cs_vocab_sample_ex(rows = S,
+ * n_draw = 1) with the seed of cs_sample_step, on the same bias and with the seen set
+ *   seen_ids[seen_off[s] : seen_off[s+1]] (the stream's prompt tokens; seen_off [S + 1])
+ *   plus out_tokens[s][0 : out_len[s]] as they stand when the call starts,
+ * so the set grows from step to step by itself.  temperature == 0 is greedy: base_seeds and
+ * the step's value are not used for the draw.
+ * The state update is cs_sample_step's, and then, if the token was appended and
+ * n_stop_seq > 0: with the window tail[s][0 : tail_len[s]] ++ bytes(id), where bytes(v) =
+ * tok_bytes[tok_off[v] : tok_off[v+1]] (uint8 / int32 [vocab + 1], device), done[s] = 1 if
+ * one of the stop strings occurs in the window ending inside the new token's bytes (the token
+ * stays appended, so a host that cuts the text sees the whole occurrence; next_tok[s] =
+ * pad_id).  The new tail is the last min(31, length) bytes of the window.  A token with no
+ * bytes (a special token) changes nothing.  tail is uint8 [S][32], tail_len int32 [S], both
+ * device memory, zero before a stream's first step.
+ * The stop strings are HOST memory, copied into the launch: string k is
+ * stop_bytes[stop_off[k] : stop_off[k+1]], stop_off[0] = 0, n_stop_seq <= 8 strings of 1 to
+ * 32 bytes.  With n_stop_seq == 0 none of tok_bytes, tok_off, stop_bytes, stop_off, tail and
+ * tail_len is read.
+ * With temperature > 0, penalty 1 and n_stop_seq == 0 the call IS cs_sample_step: same
+ * kernels, same bits.
+ * Limits and workspace: those of cs_sample_step (the same size), penalty finite and > 0, and
+ * at most 2^19 tokens per row slice whether or not a bias is given.
+ *
+ * Replaces: temperature=0, repetition_penalty and stop of the remote completion call behind
+ *   generate_text (src/utils.py:77-198), as the Habermas Machine's ranking prediction
+ *   (src/methods/habermas_machine.py:948) and the evaluator's judges use them.
+ */
+size_t cs_sample_step_ex_workspace_size(int64_t S, int64_t vocab);
+int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, int64_t ld,
+                      float temperature, float softcap, const uint64_t* base_seeds,
+                      const int32_t* step, const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                      float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                      const int32_t* stop_ids, int32_t n_stop, const uint8_t* tok_bytes,
+                      const int32_t* tok_off, const uint8_t* stop_bytes, const int32_t* stop_off,
+                      int32_t n_stop_seq, uint8_t* tail, int32_t* tail_len, int32_t max_tokens,
+                      int32_t pad_id, int32_t* done, int32_t* out_len, int32_t* out_tokens,
+                      float* out_lp, int64_t* next_tok, int32_t* n_alive, void* workspace,
+                      size_t workspace_bytes, cs_stream_t stream);
+
+/*
  * cs_prefix_attention — cascade attention of many candidate streams over SHARED
  * per-agent prefix K/V (bf16 in / bf16 out, fp32 online softmax, bf16 MFMA).
  *
