@@ -63,11 +63,14 @@ inline bool misaligned(const void* p, int a) { return reinterpret_cast<uintptr_t
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Launch of a kernel that may take more dynamic LDS than the default 64 KiB: the limit is raised
-// to `limit` once per process and kernel (a template argument: one static per instantiation)
-template <auto Kernel, typename... Args>
+// to `limit` once per process and kernel (a template argument: one static per instantiation).
+// RaiseAbove: a kernel with static arrays beside its dynamic LDS meets the default sooner.
+// Once per PROCESS: right for this project, which runs one process per GPU.  A process that
+// launched on a second device would have to raise the limit there as well.
+template <auto Kernel, size_t RaiseAbove = 64 * 1024, typename... Args>
 inline void launch_big_lds(size_t limit, dim3 grid, dim3 block, size_t lds, hipStream_t st,
                            Args... args) {
-  if (lds > 64 * 1024) {
+  if (lds > RaiseAbove) {
     static const hipError_t raised =
         hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(limit));

@@ -151,18 +151,13 @@ __device__ __forceinline__ void draw_merge(float& s, int32_t& i, float s2, int32
   }
 }
 
-// What cs_sample_step adds to the streaming stage (SampleMode > kSamplePlain): the row's one
-// seed is derived on the device from (base seed, *step), a finished stream's workgroups leave
-// before they touch its row, and (kSampleStepBias) the listed tokens take bias_value in fp32
-// before the soft-cap, looked up in an LDS bitmap over the workgroup's slice of the vocabulary.
-// What the *_ex entries add (kSamplePlainEx, kSampleStepEx): a second bitmap beside the bias
-// one marks the row's seen tokens, which take the repetition penalty after the soft-cap, and
-// with `greedy` the score is the transformed logit itself (no seed read, no Gumbel noise).
-enum SampleMode {
-  kSamplePlain = 0, kSampleStep = 1, kSampleStepBias = 2, kSamplePlainEx = 3, kSampleStepEx = 4
-};
-constexpr bool mode_is_step(int m) { return m == kSampleStep || m == kSampleStepBias || m == kSampleStepEx; }
-constexpr bool mode_is_ex(int m) { return m == kSamplePlainEx || m == kSampleStepEx; }
+// The streaming stage's two template axes.  STEP (cs_sample_step, cs_sample_step_ex): the row's
+// one seed is derived on the device from (base seed, *step), and a finished stream's workgroups
+// leave before they touch its row.  TABLES: how many LDS bitmaps over the workgroup's slice of
+// the vocabulary.  1 (cs_sample_step with a bias list): the listed tokens take bias_value in
+// fp32 before the soft-cap.  2 (the *_ex entries): a second bitmap marks the row's seen tokens,
+// which take the repetition penalty after the soft-cap, and with `greedy` the score is the
+// transformed logit itself (no seed read, no Gumbel noise).
 struct StepIn {
   const int32_t* step;
   const int32_t* done;
@@ -212,9 +207,10 @@ __device__ __forceinline__ bool wave_seen(const StepIn& in, int64_t row, int32_t
   return hit;
 }
 
-// token i's transformed logit, as the streaming stage of the *_ex modes computes it
+// Token i's transformed logit: the one statement of the rule, for the streaming stage and for
+// every log-probability (no list: biased = seen = false)
 template <int DT, bool CAP>
-__device__ __forceinline__ float ex_logit(const char* rp, int32_t i, bool biased, bool seen,
+__device__ __forceinline__ float ex_logit(const char* rp, int64_t i, bool biased, bool seen,
                                           const StepIn& in, float cap, float inv_cap) {
   float x = load_any<DT>(rp, i);
   if (biased) x += in.bias_value;
@@ -223,53 +219,53 @@ __device__ __forceinline__ float ex_logit(const char* rp, int32_t i, bool biased
   return x;
 }
 
-template <int DT, bool CAP, int MODE>
+// the LDS bitmaps: one bit per token of the workgroup's slice [v0, v1)
+__device__ __forceinline__ void mark(uint32_t* bits, int64_t id, int64_t v0, int64_t v1) {
+  if (id >= v0 && id < v1) atomicOr(&bits[(id - v0) >> 5], 1u << ((id - v0) & 31));
+}
+__device__ __forceinline__ bool marked(const uint32_t* bits, int64_t o) {
+  return (bits[o >> 5] >> (o & 31)) & 1u;
+}
+
+template <int DT, bool CAP, bool STEP, int TABLES>
 __global__ __launch_bounds__(256) void vocab_sample_kernel(
     const char* __restrict__ logits, int64_t vocab, int64_t ld_bytes, int32_t nsplit,
     int64_t split_len, float inv_temp, float cap, float inv_cap,
     const unsigned long long* __restrict__ seeds, int32_t n_draw, float2* __restrict__ lse_part,
     DrawBest* __restrict__ draw_part, StepIn in) {
-  // kSampleStepBias: one bit per token of [v0, v1); the *_ex modes: the seen bitmap after it
-  extern __shared__ uint32_t sm_bias[];
+  extern __shared__ uint32_t sm_bias[];   // TABLES >= 1; the seen bitmap (TABLES == 2) after it
   __shared__ float sm_m[4], sm_s[4];
   __shared__ float sm_bs[4][kMaxDraws];
   __shared__ int32_t sm_bi[4][kMaxDraws];
   const int tid = threadIdx.x;
   const int64_t bid = blockIdx.x;
   const int64_t row = bid / nsplit;
-  if (mode_is_step(MODE) && in.done[row] != 0) return;   // block-uniform, before any barrier
+  if (STEP && in.done[row] != 0) return;   // block-uniform, before any barrier
   const int32_t split = static_cast<int32_t>(bid - row * nsplit);
   const char* rp = logits + row * ld_bytes;
   const int64_t v0 = static_cast<int64_t>(split) * split_len;
   const int64_t v1 = min(vocab, v0 + split_len);
   const int nw = static_cast<int>((v1 - v0 + 31) >> 5);
   uint32_t* sm_seen = sm_bias + nw;
-  if (MODE == kSampleStepBias || mode_is_ex(MODE)) {
-    for (int w = tid; w < (mode_is_ex(MODE) ? 2 * nw : nw); w += 256) sm_bias[w] = 0u;
+  if (TABLES > 0) {
+    for (int w = tid; w < TABLES * nw; w += 256) sm_bias[w] = 0u;
     __syncthreads();
-    for (int j = tid; j < in.n_bias; j += 256) {
-      const int64_t id = in.bias_ids[j];
-      if (id >= v0 && id < v1) atomicOr(&sm_bias[(id - v0) >> 5], 1u << ((id - v0) & 31));
-    }
-    if (mode_is_ex(MODE) && in.penalty != 1.0f) {
+    for (int j = tid; j < in.n_bias; j += 256) mark(sm_bias, in.bias_ids[j], v0, v1);
+    if (TABLES == 2 && in.penalty != 1.0f) {
       if (in.seen_off) {
         const int64_t b = in.seen_off[row + 1];
-        for (int64_t j = in.seen_off[row] + tid; j < b; j += 256) {
-          const int64_t id = in.seen_ids[j];
-          if (id >= v0 && id < v1) atomicOr(&sm_seen[(id - v0) >> 5], 1u << ((id - v0) & 31));
-        }
+        for (int64_t j = in.seen_off[row] + tid; j < b; j += 256)
+          mark(sm_seen, in.seen_ids[j], v0, v1);
       }
-      if (MODE == kSampleStepEx) {
+      if (STEP) {
         const int32_t len = seen_out_len(in.out_len[row], in.max_tokens);
-        for (int j = tid; j < len; j += 256) {
-          const int64_t id = in.out_tokens[row * in.max_tokens + j];
-          if (id >= v0 && id < v1) atomicOr(&sm_seen[(id - v0) >> 5], 1u << ((id - v0) & 31));
-        }
+        for (int j = tid; j < len; j += 256)
+          mark(sm_seen, in.out_tokens[row * in.max_tokens + j], v0, v1);
       }
     }
     __syncthreads();
   }
-  const bool greedy = mode_is_ex(MODE) && in.greedy != 0;
+  const bool greedy = TABLES == 2 && in.greedy != 0;
   unsigned long long sd[kMaxDraws];
   float bs[kMaxDraws];
   int32_t bi[kMaxDraws];
@@ -279,21 +275,14 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
     bs[d] = -INFINITY;
     bi[d] = 0x7fffffff;
   }
-  if (mode_is_step(MODE) && !greedy)   // n_draw = 1
+  if (STEP && !greedy)   // n_draw = 1
     sd[0] = sd[0] * kSeedMul + static_cast<unsigned long long>(static_cast<int64_t>(*in.step));
   float m = -INFINITY, s = 0.0f;
   bool saw_nan = false;
   for (int64_t v = v0 + tid; v < v1; v += 256) {
-    float x = load_any<DT>(rp, v);
-    const int64_t o = v - v0;
-    if (MODE == kSampleStepBias || mode_is_ex(MODE)) {
-      if ((sm_bias[o >> 5] >> (o & 31)) & 1u) x += in.bias_value;
-    }
-    if (CAP) x = softcap_fn(x, cap, inv_cap);
-    if (mode_is_ex(MODE)) {
-      if ((sm_seen[o >> 5] >> (o & 31)) & 1u) x = penalise(x, in.penalty);
-    }
-    const float y = x * inv_temp;
+    const bool biased = TABLES > 0 && marked(sm_bias, v - v0);
+    const bool seen = TABLES == 2 && marked(sm_seen, v - v0);
+    const float y = ex_logit<DT, CAP>(rp, v, biased, seen, in, cap, inv_cap) * inv_temp;
     saw_nan |= y != y;
     lse_accum<1>(m, s, &y);
 #pragma unroll
@@ -352,67 +341,66 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
   }
 }
 
-// EX (cs_vocab_sample_ex): the drawn token's log-probability is taken on its transformed
-// logit, so the wave looks every draw's id up in the bias and seen lists.
-template <int DT, bool CAP, bool EX = false>
-__global__ __launch_bounds__(64) void vocab_sample_merge_kernel(
-    const char* __restrict__ logits, int64_t ld_bytes, int32_t nsplit, float inv_temp, float cap,
-    float inv_cap, const float2* __restrict__ lse_part, const DrawBest* __restrict__ draw_part,
-    int32_t n_draw, int32_t* __restrict__ out_ids, float* __restrict__ out_lp, StepIn in) {
-  const int64_t row = blockIdx.x;
-  const int lane = threadIdx.x;
+// The split merge of every second stage, called by a whole wave: the row's lse (to every lane)
+// and draw column `col` merged in split order, so that ties keep the lower token id.  One
+// body, so the plain and the step entries agree on the id and on the lse bit for bit.  No
+// split offered a candidate (every logit -inf or NaN), or col >= n_draw: idx 0x7fffffff.
+__device__ __forceinline__ DrawBest merge_splits(const float2* __restrict__ lse_part,
+                                                 const DrawBest* __restrict__ draw_part,
+                                                 int64_t row, int32_t nsplit, int32_t n_draw,
+                                                 int32_t col, int lane, float& lse) {
   float m = -INFINITY, s = 0.0f;
   for (int j = lane; j < nsplit; j += 64) {
     const float2 p = lse_part[row * nsplit + j];
     lse_merge(m, s, p.x, p.y);
   }
   wave_lse_reduce(m, s);
-  const float lse = m + logf(s);
-  if (EX) {
-    float b = -INFINITY;
-    int32_t i = 0x7fffffff;
-    if (lane < n_draw) {   // n_draw <= 16: lane d merges draw d, in split order as below
-      for (int j = 0; j < nsplit; ++j) {
-        const DrawBest p = draw_part[(row * nsplit + j) * n_draw + lane];
-        draw_merge(b, i, p.s, p.idx);
-      }
-    }
-    for (int d = 0; d < n_draw; ++d) {
-      const int32_t id = __shfl(i, d, 64);
-      const bool none = id == 0x7fffffff;
-      const bool biased = wave_listed(in.bias_ids, in.n_bias, id, lane);
-      const bool seen = wave_seen(in, row, id, lane, nullptr, 0);
-      if (lane == d) {
-        out_ids[row * n_draw + d] = none ? -1 : id;
-        if (out_lp) {
-          float lp = __builtin_nanf("");
-          if (!none)
-            lp = ex_logit<DT, CAP>(logits + row * ld_bytes, id, biased, seen, in, cap, inv_cap) *
-                     inv_temp - lse;
-          out_lp[row * n_draw + d] = lp;
-        }
-      }
-    }
-    return;
-  }
-  for (int d = lane; d < n_draw; d += 64) {
-    float b = -INFINITY;
-    int32_t i = 0x7fffffff;
-    for (int j = 0; j < nsplit; ++j) {  // split order: ties keep the lower token id
-      const DrawBest p = draw_part[(row * nsplit + j) * n_draw + d];
+  lse = m + logf(s);
+  float b = -INFINITY;
+  int32_t i = 0x7fffffff;
+  if (col < n_draw) {
+    for (int j = 0; j < nsplit; ++j) {
+      const DrawBest p = draw_part[(row * nsplit + j) * n_draw + col];
       draw_merge(b, i, p.s, p.idx);
     }
-    // no split offered a candidate (every logit -inf or NaN): id -1 and NaN, nothing read
+  }
+  return DrawBest{b, i};
+}
+
+// Second stage of the plain entries, one wave per row: lane d owns draw d (n_draw <= 16).
+// EX (cs_vocab_sample_ex): the drawn token's log-probability is taken on its transformed
+// logit, so the wave looks every draw's id up in the bias and seen lists.
+template <int DT, bool CAP, bool EX>
+__global__ __launch_bounds__(64) void vocab_sample_merge_kernel(
+    const char* __restrict__ logits, int64_t ld_bytes, int32_t nsplit, float inv_temp, float cap,
+    float inv_cap, const float2* __restrict__ lse_part, const DrawBest* __restrict__ draw_part,
+    int32_t n_draw, int32_t* __restrict__ out_ids, float* __restrict__ out_lp, StepIn in) {
+  const int64_t row = blockIdx.x;
+  const int lane = threadIdx.x;
+  float lse;
+  const int32_t i = merge_splits(lse_part, draw_part, row, nsplit, n_draw, lane, lane, lse).idx;
+  bool biased = false, seen = false;
+  if constexpr (EX) {
+    for (int d = 0; d < n_draw; ++d) {
+      const int32_t id = __shfl(i, d, 64);
+      const bool b = wave_listed(in.bias_ids, in.n_bias, id, lane);
+      const bool sn = wave_seen(in, row, id, lane, nullptr, 0);
+      if (lane == d) {
+        biased = b;
+        seen = sn;
+      }
+    }
+  }
+  if (lane < n_draw) {
+    // no candidate: id -1 and NaN, nothing read
     const bool none = i == 0x7fffffff;
-    out_ids[row * n_draw + d] = none ? -1 : i;
+    out_ids[row * n_draw + lane] = none ? -1 : i;
     if (out_lp) {
       float lp = __builtin_nanf("");
-      if (!none) {
-        float x = load_any<DT>(logits + row * ld_bytes, i);
-        if (CAP) x = softcap_fn(x, cap, inv_cap);
-        lp = x * inv_temp - lse;
-      }
-      out_lp[row * n_draw + d] = lp;
+      if (!none)
+        lp = ex_logit<DT, CAP>(logits + row * ld_bytes, i, biased, seen, in, cap, inv_cap) *
+                 inv_temp - lse;
+      out_lp[row * n_draw + lane] = lp;
     }
   }
 }
@@ -462,15 +450,15 @@ __device__ __forceinline__ bool stop_window(const StopSeqs& sq, int64_t row, int
   return __ballot(hit) != 0ull;
 }
 
-// cs_sample_step's second stage, one wave per stream: the split merge of
-// vocab_sample_merge_kernel (same order, so the id and the log-prob are its bits), then the
-// stream's state update and the next step's input token.  Lane 0 of every workgroup adds
+// cs_sample_step's second stage, one wave per stream: merge_splits (so the id and the log-prob
+// are vocab_sample_merge_kernel's bits), then the stream's state update and the next step's
+// input token.  Lane 0 of every workgroup adds
 // (1 << 32 | still alive) to the workspace's one counter word; the last arrival has the
 // number of unfinished streams in the low half, writes it and leaves the word at zero.
 // EX (cs_sample_step_ex): the log-probability is taken on the transformed logit (bias,
 // soft-cap, penalty over the seen list and the tokens generated so far), and an appended
 // token runs the stop-string window.
-template <int DT, bool CAP, bool EX = false>
+template <int DT, bool CAP, bool EX>
 __global__ __launch_bounds__(64) void sample_step_merge_kernel(
     const char* __restrict__ logits, int64_t ld_bytes, int32_t nsplit, float inv_temp, float cap,
     float inv_cap, const float2* __restrict__ lse_part, const DrawBest* __restrict__ draw_part,
@@ -484,22 +472,9 @@ __global__ __launch_bounds__(64) void sample_step_merge_kernel(
   int32_t next = pad_id;
   uint32_t alive = 0u;
   if (done[row] == 0) {   // block-uniform
-    float m = -INFINITY, s = 0.0f;
-    for (int j = lane; j < nsplit; j += 64) {
-      const float2 p = lse_part[row * nsplit + j];
-      lse_merge(m, s, p.x, p.y);
-    }
-    wave_lse_reduce(m, s);
-    const float lse = m + logf(s);
-    float b = -INFINITY;
-    int32_t i = 0x7fffffff;
-    for (int j = 0; j < nsplit; ++j) {  // split order: ties keep the lower token id
-      const DrawBest p = draw_part[row * nsplit + j];
-      draw_merge(b, i, p.s, p.idx);
-    }
-    bool hit = false;
-    for (int j = lane; j < in.n_bias; j += 64) hit |= in.bias_ids[j] == i;
-    const bool biased = __ballot(hit) != 0ull;
+    float lse;
+    const int32_t i = merge_splits(lse_part, draw_part, row, nsplit, 1, 0, lane, lse).idx;
+    const bool biased = wave_listed(in.bias_ids, in.n_bias, i, lane);
     bool seen = false;
     if constexpr (EX)   // the seen set as the streaming stage saw it: before this step's append
       seen = wave_seen(in, row, i, lane, out_tokens + row * max_tokens,
@@ -515,17 +490,9 @@ __global__ __launch_bounds__(64) void sample_step_merge_kernel(
       } else {
         const int64_t at = row * max_tokens + len;
         out_tokens[at] = i;
-        if (out_lp) {
-          if constexpr (EX) {
-            out_lp[at] = ex_logit<DT, CAP>(logits + row * ld_bytes, i, biased, seen, in, cap,
-                                           inv_cap) * inv_temp - lse;
-          } else {
-            float x = load_any<DT>(logits + row * ld_bytes, i);
-            if (biased) x += in.bias_value;
-            if (CAP) x = softcap_fn(x, cap, inv_cap);
-            out_lp[at] = x * inv_temp - lse;
-          }
-        }
+        if (out_lp)
+          out_lp[at] = ex_logit<DT, CAP>(logits + row * ld_bytes, i, biased, seen, in, cap,
+                                         inv_cap) * inv_temp - lse;
         out_len[row] = len + 1;
         appended = 1;
         if (len + 1 == max_tokens) {
@@ -561,24 +528,127 @@ int32_t topk_nchunk(int64_t vocab) {
   return static_cast<int32_t>((vocab + kTopkChunk - 1) / kTopkChunk);
 }
 
-// The two bitmaps of an *_ex slice, and their launch: beside the kernel's static arrays they
-// pass the default 64 KiB of LDS from about 2^18 tokens per slice, so the limit is raised
-// (once per kernel) before the default is met.
-size_t ex_lds_bytes(int64_t split_len) {
-  return 2 * static_cast<size_t>((split_len + 31) / 32) * sizeof(uint32_t);
+// What the four sampling entries share once their own argument checks have passed:
+// cs_vocab_sample's split plan (for every entry and dtype: one plan is what makes their bits
+// one), the workspace carved into [arrival word |] lse_part | draw_part, and the launches'
+// scalars.
+struct SampleCall {
+  int dtype;
+  SplitPlan plan;
+  uint32_t rows, grid;            // grid: one streaming workgroup per (row, split)
+  unsigned long long* arrivals;   // the step entries' counter word
+  float2* lse_part;
+  DrawBest* draw_part;
+  const char* lg;
+  int64_t vocab, ld_bytes;
+  float cap, inv_cap, inv_t;
+  const unsigned long long* seeds;
+  int32_t n_draw;
+  hipStream_t st;
+};
+
+// `slice_msg`: the entry's text for a slice that outgrows its LDS bitmaps, NULL without bitmaps.
+// temperature 0 (greedy, the *_ex entries) scores the logit itself.
+int plan_sample(SampleCall& c, const char* fn, const void* logits, int dtype, int64_t rows,
+                int64_t vocab, int64_t ld, float temperature, float softcap, const uint64_t* seeds,
+                int32_t n_draw, void* workspace, size_t workspace_bytes, bool arrival_word,
+                const char* slice_msg, cs_stream_t stream) {
+  c.plan = plan_split(rows, vocab, CS_F32);   // elementwise loop: same split for every dtype
+  if (int rc = check_grid(fn, rows * c.plan.nsplit)) return rc;
+  if (slice_msg && c.plan.split_len > kMaxBiasSlice)
+    return fail(CS_ERR_INVALID, std::string(fn) + slice_msg);
+  const size_t head = arrival_word ? sizeof(unsigned long long) : 0;
+  if (int rc = check_workspace(fn, workspace, workspace_bytes,
+                               head + cs_vocab_sample_workspace_size(rows, vocab, n_draw)))
+    return rc;
+  c.dtype = dtype;
+  c.rows = static_cast<uint32_t>(rows);
+  c.grid = static_cast<uint32_t>(rows * c.plan.nsplit);
+  c.arrivals = static_cast<unsigned long long*>(workspace);
+  c.lse_part = reinterpret_cast<float2*>(static_cast<char*>(workspace) + head);
+  c.draw_part = reinterpret_cast<DrawBest*>(c.lse_part + rows * c.plan.nsplit);
+  c.lg = static_cast<const char*>(logits);
+  c.vocab = vocab;
+  c.ld_bytes = ld * elt_size(dtype);
+  c.cap = softcap;
+  c.inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
+  c.inv_t = temperature == 0.0f ? 1.0f : 1.0f / temperature;
+  c.seeds = reinterpret_cast<const unsigned long long*>(seeds);
+  c.n_draw = n_draw;
+  c.st = static_cast<hipStream_t>(stream);
+  return CS_OK;
 }
-// The attribute is set once per PROCESS and instantiation (a function-local static): right for
-// this project, which runs one process per GPU.  A process that launched on a second device
-// would have to raise the limit there as well; a refusal shows only as the launch's own error.
-template <auto Kernel, typename... Args>
-void launch_tables(dim3 grid, size_t lds, hipStream_t st, Args... args) {
-  if (lds > 60 * 1024) {
-    static const hipError_t raised =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kExLdsLimit));
-    (void)raised;  // a refusal shows as the launch's own error
-  }
-  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, st, args...);
+
+// The streaming stage.  Beside the kernel's static arrays the two bitmaps of an *_ex slice pass
+// the default 64 KiB of LDS from about 2^18 tokens (the one bitmap of a biased step at 2^19),
+// so the limit is raised before it is met.
+template <int DT, bool CAP, bool STEP, int TABLES>
+void launch_stream(const SampleCall& c, const StepIn& in) {
+  const size_t lds = TABLES * static_cast<size_t>((c.plan.split_len + 31) / 32) * sizeof(uint32_t);
+  launch_big_lds<&vocab_sample_kernel<DT, CAP, STEP, TABLES>, 60 * 1024>(
+      kExLdsLimit, dim3(c.grid), dim3(256), lds, c.st, c.lg, c.vocab, c.ld_bytes, c.plan.nsplit,
+      c.plan.split_len, c.inv_t, c.cap, c.inv_cap, c.seeds, c.n_draw, c.lse_part, c.draw_part, in);
+}
+
+// both stages of the plain entries (TABLES 0: cs_vocab_sample, 2: cs_vocab_sample_ex)
+template <int TABLES>
+int launch_plain(const char* fn, const SampleCall& c, const StepIn& in, int32_t* out_ids,
+                 float* out_lp) {
+  dispatch_dtype_cap(c.dtype, c.cap, [&](auto dt, auto cap) {
+    constexpr int DT = decltype(dt)::value;
+    constexpr bool CAP = decltype(cap)::value;
+    launch_stream<DT, CAP, false, TABLES>(c, in);
+    hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP, TABLES == 2>), dim3(c.rows), dim3(64), 0,
+                       c.st, c.lg, c.ld_bytes, c.plan.nsplit, c.inv_t, c.cap, c.inv_cap, c.lse_part,
+                       c.draw_part, c.n_draw, out_ids, out_lp, in);
+  });
+  return check_launch(fn);
+}
+
+// the state arguments of the two step entries
+struct StepState {
+  const int32_t* stop_ids;
+  int32_t n_stop, max_tokens, pad_id;
+  int32_t *done, *out_len, *out_tokens;
+  float* out_lp;   // optional
+  int64_t* next_tok;
+  int32_t* n_alive;
+};
+
+// `bad_counts`: the entry's own text when one of its list counts is out of range, else NULL
+int check_step_state(const char* fn, int64_t S, int64_t vocab, const StepState& s,
+                     const char* bad_counts) {
+  if (S < 0) return fail(CS_ERR_INVALID, std::string(fn) + ": need S >= 0");
+  if (bad_counts) return fail(CS_ERR_INVALID, std::string(fn) + bad_counts);
+  if (s.max_tokens < 1) return fail(CS_ERR_INVALID, std::string(fn) + ": need max_tokens >= 1");
+  if (s.pad_id < 0 || s.pad_id >= vocab)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": pad_id outside [0, vocab)");
+  return CS_OK;
+}
+
+// a greedy step reads no seed
+bool step_ptr_missing(const void* logits, const uint64_t* base_seeds, bool greedy, const StepIn& in,
+                      const StepState& s) {
+  return !logits || (!greedy && !base_seeds) || !in.step || !s.done || !s.out_len ||
+         !s.out_tokens || !s.next_tok || !s.n_alive || (in.n_bias > 0 && !in.bias_ids) ||
+         (s.n_stop > 0 && !s.stop_ids);
+}
+
+// both stages of the step entries (TABLES 0 or 1: cs_sample_step, 2: cs_sample_step_ex)
+template <int TABLES, typename Seqs>
+int launch_step(const char* fn, const SampleCall& c, const StepIn& in, const StepState& s,
+                const Seqs& sq) {
+  dispatch_dtype_cap(c.dtype, c.cap, [&](auto dt, auto cap) {
+    constexpr int DT = decltype(dt)::value;
+    constexpr bool CAP = decltype(cap)::value;
+    launch_stream<DT, CAP, true, TABLES>(c, in);
+    hipLaunchKernelGGL((sample_step_merge_kernel<DT, CAP, TABLES == 2>), dim3(c.rows), dim3(64), 0,
+                       c.st, c.lg, c.ld_bytes, c.plan.nsplit, c.inv_t, c.cap, c.inv_cap, c.lse_part,
+                       c.draw_part, in, s.stop_ids, s.n_stop, s.max_tokens, s.pad_id, s.done,
+                       s.out_len, s.out_tokens, s.out_lp, reinterpret_cast<long long*>(s.next_tok),
+                       s.n_alive, c.arrivals, sq);
+  });
+  return check_launch(fn);
 }
 
 // temperature 0 is greedy; a penalty of 1 is off
@@ -658,31 +728,11 @@ int cs_vocab_sample(const void* logits, int dtype, int64_t rows, int64_t vocab, 
   if (int rc = check_softcap(fn, softcap)) return rc;
   if (rows == 0) return CS_OK;
   if (!logits || !seeds || !out_ids) return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
-  const SplitPlan plan = plan_split(rows, vocab, CS_F32);
-  if (int rc = check_grid(fn, rows * plan.nsplit)) return rc;
-  if (int rc = check_workspace(fn, workspace, workspace_bytes,
-                               cs_vocab_sample_workspace_size(rows, vocab, n_draw)))
+  SampleCall c;
+  if (int rc = plan_sample(c, fn, logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
+                           workspace, workspace_bytes, false, nullptr, stream))
     return rc;
-  auto* lse_part = static_cast<float2*>(workspace);
-  auto* draw_part = reinterpret_cast<DrawBest*>(lse_part + rows * plan.nsplit);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t ld_bytes = ld * elt_size(dtype);
-  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
-  const float inv_t = 1.0f / temperature;
-  const char* lg = static_cast<const char*>(logits);
-  const auto* sd = reinterpret_cast<const unsigned long long*>(seeds);
-  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
-    constexpr int DT = decltype(dt)::value;
-    constexpr bool CAP = decltype(cap)::value;
-    hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP, kSamplePlain>),
-                       dim3(static_cast<uint32_t>(rows * plan.nsplit)), dim3(256), 0, st, lg, vocab,
-                       ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap, sd, n_draw,
-                       lse_part, draw_part, StepIn{});
-    hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(rows)), dim3(64),
-                       0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part, draw_part,
-                       n_draw, out_ids, out_lp, StepIn{});
-  });
-  return check_launch("cs_vocab_sample");
+  return launch_plain<0>(fn, c, StepIn{}, out_ids, out_lp);
 }
 
 // workspace: the arrival word, then the partials of cs_vocab_sample with one draw
@@ -699,55 +749,27 @@ int cs_sample_step(const void* logits, int dtype, int64_t S, int64_t vocab, int6
                    int64_t* next_tok, int32_t* n_alive, void* workspace, size_t workspace_bytes,
                    cs_stream_t stream) {
   const char* fn = "cs_sample_step";
+  const StepIn in{step, done, bias_ids, n_bias, bias_value};
+  const StepState state{stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
+                        next_tok, n_alive};
   if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
-  if (S < 0) return fail(CS_ERR_INVALID, std::string(fn) + ": need S >= 0");
-  if (n_bias < 0 || n_bias > 1024 || n_stop < 0 || n_stop > 16)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 <= n_bias <= 1024 and 0 <= n_stop <= 16");
-  if (max_tokens < 1) return fail(CS_ERR_INVALID, std::string(fn) + ": need max_tokens >= 1");
-  if (pad_id < 0 || pad_id >= vocab)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": pad_id outside [0, vocab)");
+  const bool bad_counts = n_bias < 0 || n_bias > 1024 || n_stop < 0 || n_stop > 16;
+  if (int rc = check_step_state(fn, S, vocab, state,
+                                bad_counts ? ": need 0 <= n_bias <= 1024 and 0 <= n_stop <= 16" : nullptr))
+    return rc;
   if (!(temperature > 0.0f) || std::isinf(temperature))
     return fail(CS_ERR_INVALID, std::string(fn) + ": temperature must be finite and > 0");
   if (int rc = check_softcap(fn, softcap)) return rc;
   if (S == 0) return CS_OK;
-  if (!logits || !base_seeds || !step || !done || !out_len || !out_tokens || !next_tok || !n_alive ||
-      (n_bias > 0 && !bias_ids) || (n_stop > 0 && !stop_ids))
+  if (step_ptr_missing(logits, base_seeds, false, in, state))
     return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
-  const SplitPlan plan = plan_split(S, vocab, CS_F32);   // cs_vocab_sample's, for its bits
-  if (int rc = check_grid(fn, S * plan.nsplit)) return rc;
-  if (n_bias > 0 && plan.split_len > kMaxBiasSlice)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": a biased row slice exceeds 2^19 tokens");
-  if (int rc = check_workspace(fn, workspace, workspace_bytes, cs_sample_step_workspace_size(S, vocab)))
+  SampleCall c;
+  if (int rc = plan_sample(c, fn, logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, 1,
+                           workspace, workspace_bytes, true,
+                           n_bias > 0 ? ": a biased row slice exceeds 2^19 tokens" : nullptr, stream))
     return rc;
-  auto* arrivals = static_cast<unsigned long long*>(workspace);
-  auto* lse_part = reinterpret_cast<float2*>(arrivals + 1);
-  auto* draw_part = reinterpret_cast<DrawBest*>(lse_part + S * plan.nsplit);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t ld_bytes = ld * elt_size(dtype);
-  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
-  const float inv_t = 1.0f / temperature;
-  const char* lg = static_cast<const char*>(logits);
-  const auto* sd = reinterpret_cast<const unsigned long long*>(base_seeds);
-  const StepIn in{step, done, bias_ids, n_bias, bias_value};
-  const dim3 grid(static_cast<uint32_t>(S * plan.nsplit));
-  const size_t bitmap = static_cast<size_t>((plan.split_len + 31) / 32) * sizeof(uint32_t);
-  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
-    constexpr int DT = decltype(dt)::value;
-    constexpr bool CAP = decltype(cap)::value;
-    if (n_bias > 0)
-      hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP, kSampleStepBias>), grid, dim3(256), bitmap, st,
-                         lg, vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap,
-                         sd, 1, lse_part, draw_part, in);
-    else
-      hipLaunchKernelGGL((vocab_sample_kernel<DT, CAP, kSampleStep>), grid, dim3(256), 0, st, lg,
-                         vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap, sd,
-                         1, lse_part, draw_part, in);
-    hipLaunchKernelGGL((sample_step_merge_kernel<DT, CAP>), dim3(static_cast<uint32_t>(S)), dim3(64),
-                       0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part, draw_part,
-                       in, stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
-                       reinterpret_cast<long long*>(next_tok), n_alive, arrivals, NoStopSeqs{});
-  });
-  return check_launch("cs_sample_step");
+  return n_bias > 0 ? launch_step<1>(fn, c, in, state, NoStopSeqs{})
+                    : launch_step<0>(fn, c, in, state, NoStopSeqs{});
 }
 
 size_t cs_vocab_sample_ex_workspace_size(int64_t rows, int64_t vocab, int32_t n_draw) {
@@ -775,21 +797,11 @@ int cs_vocab_sample_ex(const void* logits, int dtype, int64_t rows, int64_t voca
   if (!greedy && !penalised && n_bias == 0)   // every control off: the old entry, its kernels
     return cs_vocab_sample(logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
                            out_ids, out_lp, workspace, workspace_bytes, stream);
-  const SplitPlan plan = plan_split(rows, vocab, CS_F32);
-  if (int rc = check_grid(fn, rows * plan.nsplit)) return rc;
-  if (plan.split_len > kMaxBiasSlice)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": a biased or penalised row slice exceeds 2^19 tokens");
-  if (int rc = check_workspace(fn, workspace, workspace_bytes,
-                               cs_vocab_sample_workspace_size(rows, vocab, n_draw)))
+  SampleCall c;
+  if (int rc = plan_sample(c, fn, logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
+                           workspace, workspace_bytes, false,
+                           ": a biased or penalised row slice exceeds 2^19 tokens", stream))
     return rc;
-  auto* lse_part = static_cast<float2*>(workspace);
-  auto* draw_part = reinterpret_cast<DrawBest*>(lse_part + rows * plan.nsplit);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t ld_bytes = ld * elt_size(dtype);
-  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
-  const float inv_t = greedy ? 1.0f : 1.0f / temperature;
-  const char* lg = static_cast<const char*>(logits);
-  const auto* sd = reinterpret_cast<const unsigned long long*>(seeds);
   StepIn in{};
   in.bias_ids = bias_ids;
   in.n_bias = n_bias;
@@ -798,18 +810,7 @@ int cs_vocab_sample_ex(const void* logits, int dtype, int64_t rows, int64_t voca
   in.seen_off = penalised ? seen_off : nullptr;
   in.penalty = penalised ? repetition_penalty : 1.0f;
   in.greedy = greedy;
-  const dim3 grid(static_cast<uint32_t>(rows * plan.nsplit));
-  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
-    constexpr int DT = decltype(dt)::value;
-    constexpr bool CAP = decltype(cap)::value;
-    launch_tables<&vocab_sample_kernel<DT, CAP, kSamplePlainEx>>(
-        grid, ex_lds_bytes(plan.split_len), st, lg, vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap,
-        sd, n_draw, lse_part, draw_part, in);
-    hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP, true>), dim3(static_cast<uint32_t>(rows)),
-                       dim3(64), 0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part,
-                       draw_part, n_draw, out_ids, out_lp, in);
-  });
-  return check_launch(fn);
+  return launch_plain<2>(fn, c, in, out_ids, out_lp);
 }
 
 size_t cs_sample_step_ex_workspace_size(int64_t S, int64_t vocab) {
@@ -827,15 +828,14 @@ int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, i
                       float* out_lp, int64_t* next_tok, int32_t* n_alive, void* workspace,
                       size_t workspace_bytes, cs_stream_t stream) {
   const char* fn = "cs_sample_step_ex";
+  StepIn in{step, done, bias_ids, n_bias, bias_value};
+  const StepState state{stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
+                        next_tok, n_alive};
   if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
-  if (S < 0) return fail(CS_ERR_INVALID, std::string(fn) + ": need S >= 0");
-  if (n_stop < 0 || n_stop > 16)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 <= n_stop <= 16");
-  if (n_stop_seq < 0 || n_stop_seq > kMaxStopSeq)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 <= n_stop_seq <= 8");
-  if (max_tokens < 1) return fail(CS_ERR_INVALID, std::string(fn) + ": need max_tokens >= 1");
-  if (pad_id < 0 || pad_id >= vocab)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": pad_id outside [0, vocab)");
+  const char* bad_counts =
+      (n_stop < 0 || n_stop > 16) ? ": need 0 <= n_stop <= 16"
+      : (n_stop_seq < 0 || n_stop_seq > kMaxStopSeq) ? ": need 0 <= n_stop_seq <= 8" : nullptr;
+  if (int rc = check_step_state(fn, S, vocab, state, bad_counts)) return rc;
   if (int rc = check_controls(fn, temperature, repetition_penalty, n_bias)) return rc;
   if (int rc = check_softcap(fn, softcap)) return rc;
   StopSeqs sq{};
@@ -857,8 +857,7 @@ int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, i
   if (S == 0) return CS_OK;
   const bool greedy = temperature == 0.0f;
   const bool penalised = repetition_penalty != 1.0f;
-  if (!logits || (!greedy && !base_seeds) || !step || !done || !out_len || !out_tokens || !next_tok ||
-      !n_alive || (n_bias > 0 && !bias_ids) || (n_stop > 0 && !stop_ids) || (seen_off && !seen_ids) ||
+  if (step_ptr_missing(logits, base_seeds, greedy, in, state) || (seen_off && !seen_ids) ||
       (n_stop_seq > 0 && (!tok_bytes || !tok_off || !tail || !tail_len)))
     return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
   if (!greedy && !penalised && n_stop_seq == 0)   // every control off: the old entry, its kernels
@@ -866,22 +865,11 @@ int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, i
                           bias_ids, n_bias, bias_value, stop_ids, n_stop, max_tokens, pad_id, done,
                           out_len, out_tokens, out_lp, next_tok, n_alive, workspace, workspace_bytes,
                           stream);
-  const SplitPlan plan = plan_split(S, vocab, CS_F32);   // cs_vocab_sample's, for its bits
-  if (int rc = check_grid(fn, S * plan.nsplit)) return rc;
-  if (plan.split_len > kMaxBiasSlice)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": a biased or penalised row slice exceeds 2^19 tokens");
-  if (int rc = check_workspace(fn, workspace, workspace_bytes, cs_sample_step_workspace_size(S, vocab)))
+  SampleCall c;
+  if (int rc = plan_sample(c, fn, logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, 1,
+                           workspace, workspace_bytes, true,
+                           ": a biased or penalised row slice exceeds 2^19 tokens", stream))
     return rc;
-  auto* arrivals = static_cast<unsigned long long*>(workspace);
-  auto* lse_part = reinterpret_cast<float2*>(arrivals + 1);
-  auto* draw_part = reinterpret_cast<DrawBest*>(lse_part + S * plan.nsplit);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t ld_bytes = ld * elt_size(dtype);
-  const float inv_cap = softcap > 0.0f ? 1.0f / softcap : 0.0f;
-  const float inv_t = greedy ? 1.0f : 1.0f / temperature;
-  const char* lg = static_cast<const char*>(logits);
-  const auto* sd = reinterpret_cast<const unsigned long long*>(base_seeds);
-  StepIn in{step, done, bias_ids, n_bias, bias_value};
   in.seen_ids = penalised ? seen_ids : nullptr;
   in.seen_off = penalised ? seen_off : nullptr;
   in.out_tokens = out_tokens;
@@ -889,19 +877,7 @@ int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, i
   in.max_tokens = max_tokens;
   in.penalty = repetition_penalty;
   in.greedy = greedy;
-  const dim3 grid(static_cast<uint32_t>(S * plan.nsplit));
-  dispatch_dtype_cap(dtype, softcap, [&](auto dt, auto cap) {
-    constexpr int DT = decltype(dt)::value;
-    constexpr bool CAP = decltype(cap)::value;
-    launch_tables<&vocab_sample_kernel<DT, CAP, kSampleStepEx>>(
-        grid, ex_lds_bytes(plan.split_len), st, lg, vocab, ld_bytes, plan.nsplit, plan.split_len, inv_t, softcap, inv_cap,
-        sd, 1, lse_part, draw_part, in);
-    hipLaunchKernelGGL((sample_step_merge_kernel<DT, CAP, true>), dim3(static_cast<uint32_t>(S)),
-                       dim3(64), 0, st, lg, ld_bytes, plan.nsplit, inv_t, softcap, inv_cap, lse_part,
-                       draw_part, in, stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens,
-                       out_lp, reinterpret_cast<long long*>(next_tok), n_alive, arrivals, sq);
-  });
-  return check_launch(fn);
+  return launch_step<2>(fn, c, in, state, sq);
 }
 
 }  // extern "C"

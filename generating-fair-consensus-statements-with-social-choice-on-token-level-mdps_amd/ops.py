@@ -438,28 +438,41 @@ def vocab_topk(logits: torch.Tensor, k: int, *, vocab: Optional[int] = None, sof
     return ids, vals
 
 
+def _vocab_sample(entry: str, logits, seeds, n_draw, temperature, vocab, softcap, workspace,
+                  lists=(), controls=lambda rows: ()):
+    """The body of vocab_sample and vocab_sample_ex around the C entry point ``entry``:
+    ``controls(rows)`` gives the arguments that entry takes between n_draw and out_ids, from
+    the device tensors ``lists``."""
+    L = _lib.load()
+    rows, ld, vocab = _logits_args(logits, vocab)
+    if seeds is None:
+        n_draw = 1 if n_draw is None else int(n_draw)
+    else:
+        seeds = seeds.reshape(rows, -1)
+        if seeds.dtype != torch.int64 or not seeds.is_contiguous():
+            raise CSError("seeds must be a contiguous int64 tensor [rows, n_draw]")
+        n_draw = seeds.shape[1]
+    _require_cuda(logits, seeds, *lists)
+    extra = controls(rows)
+    ids = torch.empty((rows, n_draw), dtype=torch.int32, device=logits.device)
+    lp = torch.empty((rows, n_draw), dtype=torch.float32, device=logits.device)
+    _, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _default_ws, int(getattr(L, entry + "_workspace_size")(rows, vocab, n_draw)),
+        logits.device)
+    rc = getattr(L, entry)(logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld,
+                           float(temperature), float(softcap), _ptr(seeds), n_draw, *extra,
+                           ids.data_ptr(), lp.data_ptr(), ws_ptr, ws_bytes, _stream())
+    _lib.check(rc, entry)
+    return ids, lp
+
+
 def vocab_sample(logits: torch.Tensor, seeds: torch.Tensor, *, temperature: float = 1.0,
                  vocab: Optional[int] = None, softcap: float = 0.0,
                  workspace: Optional[Workspace] = None):
     """Seeded Gumbel-max draws: seeds [rows, n_draw] int64 (bit pattern used as uint64) ->
     (ids [rows, n_draw] int32, log-probs [rows, n_draw] f32)."""
-    L = _lib.load()
-    rows, ld, vocab = _logits_args(logits, vocab)
-    seeds = seeds.reshape(rows, -1)
-    if seeds.dtype != torch.int64 or not seeds.is_contiguous():
-        raise CSError("seeds must be a contiguous int64 tensor [rows, n_draw]")
-    _require_cuda(logits, seeds)
-    n_draw = seeds.shape[1]
-    ids = torch.empty((rows, n_draw), dtype=torch.int32, device=logits.device)
-    lp = torch.empty((rows, n_draw), dtype=torch.float32, device=logits.device)
-    _, ws_ptr, ws_bytes = _workspace_args(workspace, _default_ws,
-                                          int(L.cs_vocab_sample_workspace_size(rows, vocab, n_draw)),
-                                          logits.device)
-    rc = L.cs_vocab_sample(logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld,
-                           float(temperature), float(softcap), seeds.data_ptr(), n_draw,
-                           ids.data_ptr(), lp.data_ptr(), ws_ptr, ws_bytes, _stream())
-    _lib.check(rc, "cs_vocab_sample")
-    return ids, lp
+    return _vocab_sample("cs_vocab_sample", logits, seeds, None, temperature, vocab, softcap,
+                         workspace)
 
 
 _sample_ws: dict = {}
@@ -472,6 +485,51 @@ def _state_ptr(t: Optional[torch.Tensor], name: str, dtype: torch.dtype, shape: 
     if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
         raise CSError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}")
     return t.data_ptr()
+
+
+def _id_list(t: Optional[torch.Tensor], name: str):
+    """(pointer or None, count) of an optional 1-D int32 device list."""
+    n = 0 if t is None else t.numel()
+    if n and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+        raise CSError(f"{name} must be a contiguous 1-D int32 tensor")
+    return (t.data_ptr() if n else None), n
+
+
+def _sample_step(entry: str, logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
+                 pad_id, temperature, softcap, bias_ids, bias_value, stop_ids, out_lp, max_tokens,
+                 vocab, workspace, tensors=(), penalty=lambda S: (), stop_seqs=lambda S, vocab: ()):
+    """The body of sample_step and sample_step_ex around the C entry point ``entry``:
+    ``penalty(S)`` gives the arguments that entry takes between bias_value and stop_ids,
+    ``stop_seqs(S, vocab)`` those between n_stop and max_tokens, from the device ``tensors``."""
+    L = _lib.load()
+    S, ld, vocab = _logits_args(logits, vocab)
+    _require_cuda(logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
+                  bias_ids, stop_ids, out_lp, *tensors)
+    if max_tokens is None:
+        if out_tokens is None or out_tokens.dim() != 2:
+            raise CSError("out_tokens must be [S, max_tokens] int32")
+        max_tokens = out_tokens.shape[1]
+    max_tokens = int(max_tokens)
+    bias = _id_list(bias_ids, "bias_ids")
+    stop = _id_list(stop_ids, "stop_ids")
+    seen = penalty(S)
+    workspace, ws_ptr, ws_bytes = _workspace_args(
+        workspace, _sample_ws, int(getattr(L, entry + "_workspace_size")(S, vocab)), logits.device,
+        "sample_step")
+    rc = getattr(L, entry)(
+        logits.data_ptr(), _DTYPE[logits.dtype], S, vocab, ld, float(temperature), float(softcap),
+        _state_ptr(base_seeds, "base_seeds", torch.int64, (S,)),
+        _state_ptr(step, "step", torch.int32, (1,)), *bias, float(bias_value), *seen, *stop,
+        *stop_seqs(S, vocab), max_tokens, int(pad_id),
+        _state_ptr(done, "done", torch.int32, (S,)),
+        _state_ptr(out_len, "out_len", torch.int32, (S,)),
+        _state_ptr(out_tokens, "out_tokens", torch.int32, (S, max_tokens)),
+        _state_ptr(out_lp, "out_lp", torch.float32, (S, max_tokens)),
+        _state_ptr(next_tok, "next_tok", torch.int64, (S,)),
+        _state_ptr(n_alive, "n_alive", torch.int32, (1,)), ws_ptr, ws_bytes, _stream())
+    if rc != 0:
+        workspace.reset()
+    _lib.check(rc, entry)
 
 
 def sample_step(logits: torch.Tensor, base_seeds: torch.Tensor, step: torch.Tensor,
@@ -491,46 +549,9 @@ def sample_step(logits: torch.Tensor, base_seeds: torch.Tensor, step: torch.Tens
     on the device and nothing is allocated here, so the call replays inside a captured graph.
     bias_ids / stop_ids: int32 device tensors (None or empty: none).  The workspace is a
     Workspace(zeroed=True) used by this op alone."""
-    L = _lib.load()
-    S, ld, vocab = _logits_args(logits, vocab)
-    _require_cuda(logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
-                  bias_ids, stop_ids, out_lp)
-    if max_tokens is None:
-        if out_tokens is None or out_tokens.dim() != 2:
-            raise CSError("out_tokens must be [S, max_tokens] int32")
-        max_tokens = out_tokens.shape[1]
-    max_tokens = int(max_tokens)
-    lists = []
-    for name, t in (("bias_ids", bias_ids), ("stop_ids", stop_ids)):
-        n = 0 if t is None else t.numel()
-        if n and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
-            raise CSError(f"{name} must be a contiguous 1-D int32 tensor")
-        lists += [t.data_ptr() if n else None, n]
-    dev = logits.device
-    workspace, ws_ptr, ws_bytes = _workspace_args(
-        workspace, _sample_ws, int(L.cs_sample_step_workspace_size(S, vocab)), dev, "sample_step")
-    rc = L.cs_sample_step(
-        logits.data_ptr(), _DTYPE[logits.dtype], S, vocab, ld, float(temperature), float(softcap),
-        _state_ptr(base_seeds, "base_seeds", torch.int64, (S,)),
-        _state_ptr(step, "step", torch.int32, (1,)), lists[0], lists[1], float(bias_value),
-        lists[2], lists[3], max_tokens, int(pad_id),
-        _state_ptr(done, "done", torch.int32, (S,)),
-        _state_ptr(out_len, "out_len", torch.int32, (S,)),
-        _state_ptr(out_tokens, "out_tokens", torch.int32, (S, max_tokens)),
-        _state_ptr(out_lp, "out_lp", torch.float32, (S, max_tokens)),
-        _state_ptr(next_tok, "next_tok", torch.int64, (S,)),
-        _state_ptr(n_alive, "n_alive", torch.int32, (1,)), ws_ptr, ws_bytes, _stream())
-    if rc != 0:
-        workspace.reset()
-    _lib.check(rc, "cs_sample_step")
-
-
-def _id_list(t: Optional[torch.Tensor], name: str):
-    """(pointer or None, count) of an optional 1-D int32 device list."""
-    n = 0 if t is None else t.numel()
-    if n and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
-        raise CSError(f"{name} must be a contiguous 1-D int32 tensor")
-    return (t.data_ptr() if n else None), n
+    _sample_step("cs_sample_step", logits, base_seeds, step, done, out_len, out_tokens, next_tok,
+                 n_alive, pad_id, temperature, softcap, bias_ids, bias_value, stop_ids, out_lp,
+                 max_tokens, vocab, workspace)
 
 
 def _seen_args(seen_ids: Optional[torch.Tensor], seen_off: Optional[torch.Tensor], rows: int):
@@ -559,30 +580,12 @@ def vocab_sample_ex(logits: torch.Tensor, seeds: Optional[torch.Tensor], *,
     before the soft-cap, the tokens of seen_ids[seen_off[r]:seen_off[r+1]] (int32 device
     tensors) take the repetition penalty after it, and temperature 0 is greedy (seeds may then
     be None, with n_draw giving the number of columns, default 1)."""
-    L = _lib.load()
-    rows, ld, vocab = _logits_args(logits, vocab)
-    if seeds is None:
-        n_draw = 1 if n_draw is None else int(n_draw)
-    else:
-        seeds = seeds.reshape(rows, -1)
-        if seeds.dtype != torch.int64 or not seeds.is_contiguous():
-            raise CSError("seeds must be a contiguous int64 tensor [rows, n_draw]")
-        n_draw = seeds.shape[1]
-    _require_cuda(logits, seeds, bias_ids, seen_ids, seen_off)
-    bias_ptr, n_bias = _id_list(bias_ids, "bias_ids")
-    seen_ptr, off_ptr = _seen_args(seen_ids, seen_off, rows)
-    ids = torch.empty((rows, n_draw), dtype=torch.int32, device=logits.device)
-    lp = torch.empty((rows, n_draw), dtype=torch.float32, device=logits.device)
-    _, ws_ptr, ws_bytes = _workspace_args(
-        workspace, _default_ws, int(L.cs_vocab_sample_ex_workspace_size(rows, vocab, n_draw)),
-        logits.device)
-    rc = L.cs_vocab_sample_ex(logits.data_ptr(), _DTYPE[logits.dtype], rows, vocab, ld,
-                              float(temperature), float(softcap),
-                              None if seeds is None else seeds.data_ptr(), n_draw, bias_ptr,
-                              n_bias, float(bias_value), float(repetition_penalty), seen_ptr,
-                              off_ptr, ids.data_ptr(), lp.data_ptr(), ws_ptr, ws_bytes, _stream())
-    _lib.check(rc, "cs_vocab_sample_ex")
-    return ids, lp
+    def controls(rows):
+        return (*_id_list(bias_ids, "bias_ids"), float(bias_value), float(repetition_penalty),
+                *_seen_args(seen_ids, seen_off, rows))
+
+    return _vocab_sample("cs_vocab_sample_ex", logits, seeds, n_draw, temperature, vocab, softcap,
+                         workspace, (bias_ids, seen_ids, seen_off), controls)
 
 
 MAX_STOP_SEQ, MAX_STOP_LEN = 8, 32     # cs_sample_step_ex
@@ -607,49 +610,28 @@ def sample_step_ex(logits: torch.Tensor, base_seeds: Optional[torch.Tensor], ste
     stream whose decoded bytes complete one: tok_bytes (uint8) / tok_off (int32 [vocab + 1])
     are the tokens' bytes, tail (uint8 [S, 32]) / tail_len (int32 [S]) the per-stream window,
     zero at the start.  With every control off this is ``sample_step``, bit for bit."""
-    L = _lib.load()
-    S, ld, vocab = _logits_args(logits, vocab)
-    _require_cuda(logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
-                  bias_ids, stop_ids, out_lp, seen_ids, seen_off, tok_bytes, tok_off, tail, tail_len)
-    if max_tokens is None:
-        if out_tokens is None or out_tokens.dim() != 2:
-            raise CSError("out_tokens must be [S, max_tokens] int32")
-        max_tokens = out_tokens.shape[1]
-    max_tokens = int(max_tokens)
-    bias_ptr, n_bias = _id_list(bias_ids, "bias_ids")
-    stop_ptr, n_stop = _id_list(stop_ids, "stop_ids")
-    seen_ptr, off_ptr = _seen_args(seen_ids, seen_off, S)
     stop_seqs = [bytes(b) for b in stop_seqs]
-    n_seq = len(stop_seqs)
     offs = [0]
     for b in stop_seqs:
         offs.append(offs[-1] + len(b))
     stop_bytes = ctypes.create_string_buffer(b"".join(stop_seqs), max(1, offs[-1]))
     stop_off = (ctypes.c_int32 * len(offs))(*offs)
-    dev = logits.device
-    workspace, ws_ptr, ws_bytes = _workspace_args(
-        workspace, _sample_ws, int(L.cs_sample_step_ex_workspace_size(S, vocab)), dev,
-        "sample_step")
-    rc = L.cs_sample_step_ex(
-        logits.data_ptr(), _DTYPE[logits.dtype], S, vocab, ld, float(temperature), float(softcap),
-        _state_ptr(base_seeds, "base_seeds", torch.int64, (S,)),
-        _state_ptr(step, "step", torch.int32, (1,)), bias_ptr, n_bias, float(bias_value),
-        float(repetition_penalty), seen_ptr, off_ptr, stop_ptr, n_stop,
-        _state_ptr(tok_bytes, "tok_bytes", torch.uint8,
-                   tuple(tok_bytes.shape[:1]) if tok_bytes is not None else ()),
-        _state_ptr(tok_off, "tok_off", torch.int32, (vocab + 1,)),
-        ctypes.cast(stop_bytes, ctypes.c_void_p), ctypes.cast(stop_off, ctypes.c_void_p), n_seq,
-        _state_ptr(tail, "tail", torch.uint8, (S, MAX_STOP_LEN)),
-        _state_ptr(tail_len, "tail_len", torch.int32, (S,)), max_tokens, int(pad_id),
-        _state_ptr(done, "done", torch.int32, (S,)),
-        _state_ptr(out_len, "out_len", torch.int32, (S,)),
-        _state_ptr(out_tokens, "out_tokens", torch.int32, (S, max_tokens)),
-        _state_ptr(out_lp, "out_lp", torch.float32, (S, max_tokens)),
-        _state_ptr(next_tok, "next_tok", torch.int64, (S,)),
-        _state_ptr(n_alive, "n_alive", torch.int32, (1,)), ws_ptr, ws_bytes, _stream())
-    if rc != 0:
-        workspace.reset()
-    _lib.check(rc, "cs_sample_step_ex")
+
+    def penalty(S):
+        return (float(repetition_penalty), *_seen_args(seen_ids, seen_off, S))
+
+    def seq_args(S, vocab):
+        return (_state_ptr(tok_bytes, "tok_bytes", torch.uint8,
+                           tuple(tok_bytes.shape[:1]) if tok_bytes is not None else ()),
+                _state_ptr(tok_off, "tok_off", torch.int32, (vocab + 1,)),
+                ctypes.cast(stop_bytes, ctypes.c_void_p), ctypes.cast(stop_off, ctypes.c_void_p),
+                len(stop_seqs), _state_ptr(tail, "tail", torch.uint8, (S, MAX_STOP_LEN)),
+                _state_ptr(tail_len, "tail_len", torch.int32, (S,)))
+
+    _sample_step("cs_sample_step_ex", logits, base_seeds, step, done, out_len, out_tokens, next_tok,
+                 n_alive, pad_id, temperature, softcap, bias_ids, bias_value, stop_ids, out_lp,
+                 max_tokens, vocab, workspace, (seen_ids, seen_off, tok_bytes, tok_off, tail, tail_len),
+                 penalty, seq_args)
 
 
 class AttnPlan:

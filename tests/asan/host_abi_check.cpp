@@ -183,6 +183,30 @@ static void check_rejections() {
   REJECTS(cs_vocab_sample(d, 0, 2, 128, 128, 1.f, 0.f, nullptr, 1, i, nullptr, d, 1 << 20, nullptr));
   REJECTS(cs_vocab_sample(d, 0, 2, 128, 128, 1.f, 0.f, reinterpret_cast<const uint64_t*>(d), 17, i,
                           nullptr, d, 1 << 20, nullptr));
+  // the step entries' shared state check and NULL test, the sampling entries' shared plan
+  // (a workspace of 8 bytes), and the stop strings' host arrays (0 and 33 bytes)
+  const uint64_t* u = reinterpret_cast<const uint64_t*>(d);
+  int64_t* nt = reinterpret_cast<int64_t*>(d);
+  uint8_t* b = reinterpret_cast<uint8_t*>(d);
+  const uint8_t stop_bytes[40] = {};
+  const int32_t off0[2] = {0, 0}, off33[2] = {0, 33};
+  REJECTS(cs_sample_step(d, 0, 2, 128, 128, 1.f, 0.f, u, i, nullptr, 0, 0.f, nullptr, 0, 4, 128, i, i, i,
+                         nullptr, nt, i, d, 1 << 20, nullptr));
+  REJECTS(cs_sample_step(d, 0, 2, 128, 128, 1.f, 0.f, u, i, nullptr, 0, 0.f, nullptr, 0, 4, 0, i, i, i,
+                         nullptr, nt, nullptr, d, 1 << 20, nullptr));
+  REJECTS(cs_sample_step(d, 0, 2, 128, 128, 1.f, 0.f, u, i, i, 1, 0.f, nullptr, 0, 4, 0, i, i, i,
+                         nullptr, nt, i, d, 8, nullptr));
+  REJECTS(cs_vocab_sample_ex(d, 0, 2, 128, 128, 0.f, 0.f, nullptr, 1, nullptr, 0, 0.f, 1.f, nullptr,
+                             nullptr, i, nullptr, d, 8, nullptr));
+  REJECTS(cs_sample_step_ex(d, 0, 2, 128, 128, 0.f, 0.f, nullptr, i, nullptr, 0, 0.f, 1.f, nullptr,
+                            nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                            4, 0, i, i, i, nullptr, nt, i, d, 8, nullptr));
+  REJECTS(cs_sample_step_ex(d, 0, 2, 128, 128, 1.f, 0.f, u, i, nullptr, 0, 0.f, 1.f, nullptr, nullptr,
+                            nullptr, 0, b, i, stop_bytes, off0, 1, b, i, 4, 0, i, i, i, nullptr, nt, i, d,
+                            1 << 20, nullptr));
+  REJECTS(cs_sample_step_ex(d, 0, 2, 128, 128, 1.f, 0.f, u, i, nullptr, 0, 0.f, 1.f, nullptr, nullptr,
+                            nullptr, 0, b, i, stop_bytes, off33, 1, b, i, 4, 0, i, i, i, nullptr, nt, i, d,
+                            1 << 20, nullptr));
   REJECTS(cs_beam_step(d, 0, 2, 2, 128, 128, nullptr, 4, f, 0.f, 0, 0.f, f, f, 0, nullptr, nullptr,
                        nullptr, d, 1 << 20, nullptr));
   REJECTS(cs_beam_step(d, 0, 2, 2, 128, 128, i, 4, f, 0.f, 0, 0.f, f, f, 0, nullptr, nullptr,
