@@ -20,6 +20,9 @@
 //                        store_out.  prefix_attn_lds_kernel stages every block of the
 //                        workgroup's list; prefix_attn_plan_lds_kernel stages its split's
 //                        prefix blocks and loads its tiles' history per wave.
+//                        prefix_attn_wide_kernel (described where it stands) is the no-plan
+//                        kernel's second form for scoring chunks and prefill at D = 128: 32
+//                        query rows per wave over 64-key blocks (v_mfma_f32_32x32x16_bf16).
 //   attn_merge_kernel    fixed-order merge of the key splits (no float atomics).
 //   rope_place_kernel    RoPE on the fused q|k|v projection + placement of the new K (row
 //                        layout) and V (transposed layout) into the per-stream buffers;
@@ -567,6 +570,399 @@ void prefix_attn_lds_kernel(AttnParams a) {
   CS_ATTEND_STAGED(D, a, tr, lds, nbp + hs.n, ref, qf, o, m, l);
   combine_waves<D>(tr, lds, o, m, l);
   if (tr.vrow && tr.ks == 0) store_out<D>(a, tr, o, l);
+}
+
+// ---- the wide tile: 32 query rows per wave over 64-key blocks (v_mfma_f32_32x32x16_bf16) ----
+//
+// Scoring chunks and prompt prefill at D = 128 without soft-cap or window (the rule is in
+// prefix_attention_impl).  A workgroup of kWideWaves waves holds 32 kWideWaves consecutive query
+// rows of one (group, K/V head), one 32-row tile per wave, and walks ONE list of 64-key blocks:
+// the prefix's, then those of every stream its rows touch up to the furthest query's causal
+// limit.  Per barrier and per memory round trip a wave attends 32 rows x 64 keys where
+// prefix_attn_lds_kernel's attends 16 x 32.
+//
+// Operands (32x32x16 bf16 maps: lane l, r = l & 31, h = l >> 5 holds A[r][8h + j], B[8h + j][r],
+// C[(i & 3) + 8 (i >> 2) + 4h][r] in register i): S^T = K . Q^T per 32-key half-block, so the
+// lane keeps query column r and, per half-block, the 16 keys (i & 3) + 8 (i >> 2) + 4h.
+// Registers 8s .. 8s + 7 rounded to bf16 are the B fragment of k-step s of O^T = V^T . P^T with
+// the k slots ordered key(h, j) = 16s + 8 (j >> 2) + 4h + (j & 3) -- the file header's ordering
+// argument on the 32-wide map -- and the V^T fragment of d row r is keys 16s + 4h .. + 3 and
+// 16s + 8 + 4h .. + 3 of that row.  m and l need one exchange between the two lane halves.
+//
+// LDS image of a block (32 KB, two buffers): K as 64 rows of 256 B with 16-byte chunk c of row k
+// at chunk c ^ (k & 15) (a ds_read_b128 lane group reads 16 rows distinct mod 16 at one c:
+// conflict-free); each 32-key V^T tile as D rows of 64 B in which the 8-byte key group
+// 4s + 2u + h sits at 16-byte chunk (2s + h) ^ ((d >> 2) & 3), half u: the lane's two key groups
+// of a k-step are ONE 16-byte read, and a lane group's 16 rows land in 16 different chunks of
+// the 256-byte bank window.
+//
+// Staging is through registers (no LDS DMA): block j + 2's 16-byte loads are issued after block
+// j's QK^T and written to buffer (j + 1) & 1 ... after the next barrier, which is also the one
+// that ends block j - 1's reads of that buffer: one barrier per 64 keys.  A wave skips (between
+// barriers) a staged history block that none of its own 32 rows can see.
+//
+// A 64-key block's second 32-key tile may not exist (prefixes are padded to 32 keys and ld_hist
+// is a multiple of 32, not 64): when no row of the workgroup can see a key of it, the second
+// half is staged from the block's FIRST tile again -- K / V that exist, that the first half
+// reads anyway, and that the mask hides (index >= 32 in the block is >= the limit).  No address
+// outside [0, ld_prefix) or the stream's [0, ld_hist) is ever formed.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kWideWaves = 4;        // waves (32-row tiles) per workgroup
+constexpr int kWideBlock = 64;       // keys per staged block
+
+template <int D, int NW>
+struct WideLds {
+  static_assert(D == 128, "the chunk swizzles below are written for 256-byte K rows");
+  static constexpr int NT = 64 * NW;
+  static constexpr int KBYTES = kWideBlock * D * 2;
+  static constexpr int VTILE = D * 64;                       // one 32-key V^T tile
+  static constexpr int BUF = KBYTES + 2 * VTILE;
+  static constexpr int NCH = kWideBlock * (D / 8) / NT;      // 16-byte chunks per thread per operand
+  static constexpr int QIMG = 32 * D * 2;                    // a wave's 32 rows of out
+  static_assert(NW * QIMG <= 2 * BUF, "every wave's row image fits the two key buffers");
+  static_assert(NCH >= 2 && NCH % 2 == 0, "a thread's chunks split evenly over the two tiles");
+};
+
+// the workgroup's rows as a TileRows: wave w holds rows r0 + 32w .. + 31, lane (col = l & 31,
+// h4 = l >> 5) query column col; no key striping (kw = 1) and no window
+template <int NW>
+__device__ __forceinline__ TileRows wide_rows(const AttnParams& a, int pg, int qg) {
+  TileRows r;
+  r.gi = pg / a.Hkv;
+  r.g = pg % a.Hkv;
+  const int p = a.gpfx ? a.gpfx[r.gi] : r.gi;
+  r.M = a.n_str * a.T * a.rep;
+  r.r0 = qg * 32 * NW;
+  r.nrows = min(32 * NW, r.M - r.r0);
+  r.n_qt = (r.nrows + 31) >> 5;
+  r.kw = 1;
+  const int tid = threadIdx.x;
+  r.w = tid >> 6;
+  r.lane = tid & 63;
+  r.qt = r.w;
+  r.ks = 0;
+  r.active = r.w < r.n_qt;
+  r.col = r.lane & 31;
+  r.h4 = r.lane >> 5;
+  const int row = r.r0 + r.w * 32 + r.col;
+  r.vrow = row < r.M;
+  const int rr = r.vrow ? row : r.M - 1;
+  const int jh = rr % a.rep, bt = rr / a.rep;
+  r.t = bt % a.T;
+  r.b = bt / a.T;
+  r.tok = (static_cast<int64_t>(r.gi) * a.n_str + r.b) * a.T + r.t;
+  r.head = r.g * a.rep + jh;
+  r.hb = *a.hist_base;
+  r.pl = a.plen[p];
+  r.po = a.poff[p];
+  r.hv = min(r.hb + r.t + 1, static_cast<int>(a.ldh));
+  r.kmin_pos = INT32_MIN;
+  return r;
+}
+
+// a 64-key block: the K rows and V^T tile of its two 32-key tiles (the second the first again
+// when it is not needed), its first key and the stream it belongs to (-1: the prefix)
+struct WideRef {
+  const __bf16 *k0, *vt0, *k1, *vt1;
+  int kb, bb;
+};
+
+template <int D, int NW>
+__device__ __forceinline__ void wide_fetch(const WideRef& r, u32x4 (&rk)[WideLds<D, NW>::NCH],
+                                           u32x4 (&rv)[WideLds<D, NW>::NCH]) {
+  using WL = WideLds<D, NW>;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < WL::NCH; ++j) {
+    // chunk c = tid + NT j of 1024: K row c / 16 of 64, V^T chunk c % 512 of tile c / 512
+    const bool first = j < WL::NCH / 2;
+    const int c = tid + WL::NT * (j % (WL::NCH / 2));        // the chunk inside its tile
+    rk[j] = *reinterpret_cast<const u32x4*>((first ? r.k0 : r.k1) + c * 8);
+    rv[j] = *reinterpret_cast<const u32x4*>((first ? r.vt0 : r.vt1) + c * 8);
+  }
+}
+
+template <int D, int NW>
+__device__ __forceinline__ void wide_stage(char* buf, const u32x4 (&rk)[WideLds<D, NW>::NCH],
+                                           const u32x4 (&rv)[WideLds<D, NW>::NCH]) {
+  using WL = WideLds<D, NW>;
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < WL::NCH; ++j) {
+    const int half = j < WL::NCH / 2 ? 0 : 1;
+    const int c = tid + WL::NT * (j % (WL::NCH / 2));
+    const int krow = c >> 4, kch = c & 15;
+    *reinterpret_cast<u32x4*>(buf + (half * 32 + krow) * 256 + ((kch ^ (krow & 15)) << 4)) = rk[j];
+    // V^T chunk: d row c / 4, keys 8 (c % 4) .. + 7 = key groups 2 (c % 4) (h = 0), + 1 (h = 1)
+    const int d = c >> 2, s = (c >> 1) & 1, u = c & 1, g = (d >> 2) & 3;
+    char* vrow = buf + WL::KBYTES + half * WL::VTILE + d * 64 + u * 8;
+    *reinterpret_cast<u32x2*>(vrow + (((2 * s) ^ g) << 4)) = u32x2{rv[j][0], rv[j][1]};
+    *reinterpret_cast<u32x2*>(vrow + (((2 * s + 1) ^ g) << 4)) = u32x2{rv[j][2], rv[j][3]};
+  }
+}
+
+template <int D, int NW>
+__global__ __launch_bounds__(64 * NW, 2)
+void prefix_attn_wide_kernel(AttnParams a) {
+  using WL = WideLds<D, NW>;
+  constexpr int NDS = D / 16;        // k-steps of QK^T
+  constexpr int NDT = D / 32;        // 32-row d tiles of O^T
+  __shared__ __attribute__((aligned(16))) char lds[2 * WL::BUF];
+  const int bid = logical_block(a.swizzle);
+  const TileRows tr = wide_rows<NW>(a, bid / a.n_qg, bid % a.n_qg);
+  const int row1 = tr.r0 + tr.nrows - 1;
+  const HistBlocks hs = hist_blocks(a, tr.hb, tr.r0, row1);
+  // the list: the prefix's 64-key blocks, then per stream b_lo .. b_hi those up to the
+  // stream's furthest query's causal limit -- hs.hlim (every token) for all but the last
+  // stream, whose last row of the workgroup sets its own
+  const int nbp = (tr.pl + kWideBlock - 1) / kWideBlock;
+  const int n_st = hs.n / hs.nbh;                                   // streams (hs.nbh >= 1)
+  const int hlim_last = min(tr.hb + (row1 / a.rep) % a.T + 1, static_cast<int>(a.ldh));
+  const int nbh_full = (hs.hlim + kWideBlock - 1) / kWideBlock;
+  const int nbh_last = (hlim_last + kWideBlock - 1) / kWideBlock;
+  const int n = nbp + (n_st - 1) * nbh_full + nbh_last;
+  const int r = tr.col, h = tr.h4;
+
+  // the wave's own rows (uniform): which staged history blocks any of them can see
+  const int w = __builtin_amdgcn_readfirstlane(tr.w);
+  const int wr0 = tr.r0 + 32 * w, wr1 = min(wr0 + 31, tr.M - 1);
+  const bool wact = wr0 < tr.M;
+  const int wb_lo = (wr0 / a.rep) / a.T, wb_hi = (wr1 / a.rep) / a.T, wt_hi = (wr1 / a.rep) % a.T;
+
+  const KvBase kv = kv_base(a);
+  // A place in the list, stepped with adds alone (the block references' products and
+  // quotients, formed per block, were a third of this loop's instructions): block it, from nbp
+  // on block j of the list's stream si; kb its first key and off the element offset of its
+  // first K row and V^T tile in k_pfx / vt_pfx or k_hist / vt_hist
+  struct Cursor {
+    int it, si, j, kb;
+    int64_t off;
+  };
+  const int64_t hoff0 = ((static_cast<int64_t>(tr.gi) * a.n_str + hs.b_lo) * a.Hkv + tr.g) * a.ldh * D;
+  const int64_t hstride = static_cast<int64_t>(a.Hkv) * a.ldh * D;
+  const Cursor c0 = {0, 0, 0, 0, nbp > 0 ? (static_cast<int64_t>(tr.g) * a.ldp + tr.po) * D : hoff0};
+  auto step = [&](Cursor& c) {
+    ++c.it;
+    if (c.it < nbp || (c.it > nbp && ++c.j < (c.si == n_st - 1 ? nbh_last : nbh_full))) {
+      c.kb += kWideBlock;
+      c.off += kWideBlock * D;
+    } else {                       // a stream's first block
+      if (c.it > nbp) ++c.si;
+      c.j = 0;
+      c.kb = 0;
+      c.off = hoff0 + c.si * hstride;
+    }
+  };
+  auto ref = [&](const Cursor& c) {
+    WideRef x;
+    const bool hist = c.it >= nbp;
+    const int lim = hist ? (c.si == n_st - 1 ? hlim_last : hs.hlim) : tr.pl;
+    x.k0 = (hist ? kv.kh : kv.kp) + c.off;
+    x.vt0 = (hist ? kv.vth : kv.vtp) + c.off;
+    // the second tile only where a row of the workgroup sees a key of it: it exists then
+    const bool two = c.kb + kKeyBlock < lim;
+    x.k1 = two ? x.k0 + kKeyBlock * D : x.k0;
+    x.vt1 = two ? x.vt0 + kKeyBlock * D : x.vt0;
+    x.kb = c.kb;
+    x.bb = hist ? hs.b_lo + c.si : -1;
+    return x;
+  };
+
+  // Q^T fragments: the lane's row, d 16 ds + 8h ..
+  bf16x8 qf[NDS];
+  {
+    const __bf16* qrow = a.q + (tr.tok * a.H + tr.head) * D + 8 * h;
+#pragma unroll
+    for (int ds = 0; ds < NDS; ++ds) {
+      if (tr.vrow) {
+        qf[ds] = *reinterpret_cast<const bf16x8*>(qrow + ds * 16);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[ds][e] = static_cast<__bf16>(0.0f);
+      }
+    }
+  }
+  f32x16 o[NDT];
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[dt][i] = 0.0f;
+  float m = -INFINITY, l = 0.0f;
+  const float sl2 = a.scale * kLog2e;
+
+  // this lane's fragment addresses inside a buffer: K row r (and 32 + r), chunk (2 ds + h) ^
+  // (r & 15) = (h ^ (r & 15)) ^ 2 ds; V^T row 32 dt + r, chunk (2s + h) ^ ((r >> 2) & 3)
+  const int kx = h ^ (r & 15);
+  const int vx = h ^ ((r >> 2) & 3);
+  const int koff = r * 256;
+  const int voff0 = WL::KBYTES + r * 64 + (vx << 4), voff1 = WL::KBYTES + r * 64 + ((vx ^ 2) << 4);
+
+  u32x4 rk[WL::NCH], rv[WL::NCH];
+  Cursor ca = c0, cf = c0;      // the block attended; the next one to fetch
+  // n >= 1: every row sees its own key
+  wide_fetch<D, NW>(ref(cf), rk, rv);
+  wide_stage<D, NW>(lds, rk, rv);
+  step(cf);
+  if (n > 1) {
+    wide_fetch<D, NW>(ref(cf), rk, rv);
+    step(cf);
+  }
+  for (int j = 0; j < n; ++j) {
+    __syncthreads();      // block j staged; block j - 1's reads of the other buffer done
+    if (j + 1 < n) wide_stage<D, NW>(lds + ((j + 1) & 1) * WL::BUF, rk, rv);
+    const WideRef x = ref(ca);
+    step(ca);
+    const BlockMask mk = block_mask(tr, x.kb, x.bb >= 0, x.bb);
+    // wave-uniform skip: a history block of a stream none of the wave's rows are in, or past
+    // the furthest causal limit of those that are
+    bool mine = wact;
+    if (x.bb >= 0) {
+      const int wl = (x.bb < wb_lo || x.bb > wb_hi)
+                         ? 0 : min(tr.hb + (x.bb == wb_hi ? wt_hi : a.T - 1) + 1, static_cast<int>(a.ldh));
+      mine = mine && mk.kb < wl;
+    }
+    const char* buf = lds + (j & 1) * WL::BUF;
+    f32x16 s0, s1;
+    if (mine) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s0[i] = s1[i] = 0.0f;
+      // fragment reads run two groups of four ahead of the MFMAs that use them: a read's
+      // latency hides behind the four MFMAs of the group before, not in front of its own
+      bf16x8 kf[NDS / 2][4];
+      auto read_k = [&](int g) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const char* kp = buf + koff + ((kx ^ (2 * (2 * g + e))) << 4);
+          kf[g][2 * e] = *reinterpret_cast<const bf16x8*>(kp);
+          kf[g][2 * e + 1] = *reinterpret_cast<const bf16x8*>(kp + 32 * 256);
+        }
+      };
+      read_k(0);
+      read_k(1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int g = 0; g < NDS / 2; ++g) {
+        if (g + 2 < NDS / 2) read_k(g + 2);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[g][2 * e], qf[2 * g + e], s0, 0, 0, 0);
+          s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[g][2 * e + 1], qf[2 * g + e], s1, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (j + 2 < n) {
+      wide_fetch<D, NW>(ref(cf), rk, rv);
+      step(cf);
+    }
+    if (mine) {
+      // V^T fragments of k-step g = 2c + s (half-block c), all d tiles
+      bf16x8 vf[4][NDT];
+      auto read_v = [&](int g) {
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+          vf[g][dt] = *reinterpret_cast<const bf16x8*>(buf + ((g & 1) ? voff1 : voff0) + (g >> 1) * WL::VTILE +
+                                                       dt * 32 * 64);
+      };
+      // key index i of the block is visible to the lane iff i < lim - kb; the lane's keys are
+      // 32c + (i & 3) + 8 (i >> 2) + 4h.  A block every lane sees whole skips the selects
+      const int jhi = mk.lim - mk.kb - 4 * h;
+      if (__ballot(mk.lim - mk.kb < kWideBlock) != 0) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int ki = (i & 3) + 8 * (i >> 2);
+          s0[i] = ki < jhi ? s0[i] : -INFINITY;
+          s1[i] = 32 + ki < jhi ? s1[i] : -INFINITY;
+        }
+      }
+      // max(a, b) as med3(a, b, +inf): no NaN can reach here, and fmaxf would first quiet each
+      // input (an instruction per score)
+      auto mx = [](float x, float y) { return __builtin_amdgcn_fmed3f(x, y, INFINITY); };
+      float b0 = mx(s0[0], s1[0]), b1 = mx(s0[1], s1[1]);
+#pragma unroll
+      for (int i = 2; i < 16; i += 2) {
+        b0 = mx(b0, mx(s0[i], s1[i]));
+        b1 = mx(b1, mx(s0[i + 1], s1[i + 1]));
+      }
+      float bm = mx(b0, b1);
+      bm *= sl2;                                   // log2 units (scale > 0: the max commutes)
+      {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(bm), __float_as_uint(bm), false, false);
+        bm = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+      }
+      // lazy rescale (attend_block's rule): ONE decision per 64-key block and wave, taken
+      // before any of the block's P.V, and l and O take the same factor
+      float mn = m;
+      if (__ballot(bm > m + kLazyRescale) != 0) {
+        mn = fmaxf(m, bm);
+        const float alpha = mn == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f(m - mn);
+        l *= alpha;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+      }
+      m = mn;
+      // p = 2^(s sl2 - m); a row that has seen no key yet has every s = -inf here: p = 0
+      const float ms = mn == -INFINITY ? 0.0f : mn;
+      float ps = 0.0f;
+      bf16x8 pb[2][2];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float p0 = __builtin_amdgcn_exp2f(fmaf(s0[i], sl2, -ms));
+        const float p1 = __builtin_amdgcn_exp2f(fmaf(s1[i], sl2, -ms));
+        ps += p0 + p1;
+        pb[0][i >> 3][i & 7] = static_cast<__bf16>(p0);
+        pb[1][i >> 3][i & 7] = static_cast<__bf16>(p1);
+      }
+      l += ps;
+      read_v(0);
+      read_v(1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (g + 2 < 4) read_v(g + 2);
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[g][dt], pb[g >> 1][g & 1], o[dt], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+  l += __shfl_xor(l, 32, 64);
+  // store_out's rounding on the 32-wide map: register i of d tile dt is d 32 dt + 8 (i >> 2) +
+  // 4h + (i & 3)
+  const float inv = l > 0.0f ? 1.0f / l : 0.0f;
+  // ... through the wave's own 8 KB of LDS (the key buffers are done with after the barrier),
+  // so that a store instruction writes four whole 256-byte rows: the lane's 8-byte pieces of 32
+  // rows left the chip as 16-byte fragments of 32 different rows per instruction
+  __syncthreads();
+  {
+    char* img = lds + w * WL::QIMG;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        bf16x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = static_cast<__bf16>(o[dt][4 * g + i] * inv);
+        *reinterpret_cast<bf16x4*>(img + r * 256 + (((4 * dt + g) ^ (r & 15)) << 4) + 8 * h) = v;
+      }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int64_t mine_off = tr.vrow ? (tr.tok * a.H + tr.head) * D : -1;
+    const int lr = tr.lane >> 4, ch = tr.lane & 15;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = 4 * i + lr;
+      const int64_t off = __shfl(mine_off, row, 64);      // lane row holds row row
+      const u32x4 v = *reinterpret_cast<const u32x4*>(img + row * 256 + ((ch ^ (row & 15)) << 4));
+      if (off >= 0) *reinterpret_cast<u32x4*>(a.out + off + ch * 8) = v;
+    }
+  }
 }
 
 #ifdef CS_TRACE_ATTN
@@ -1205,6 +1601,19 @@ int prefix_attention_impl(const char* name, const void* q, const void* k_prefix,
   const int64_t nwg = plan ? n_attn : base;
   a.swizzle = (!plan && nwg % 8 == 0 && nwg >= 64) ? 1 : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  // scoring chunks and prefill at D = 128 (T >= 32: the line model.forward_streams draws
+  // between them and decode), no soft-cap, no window, whole tokens per 32-row tile: the wide
+  // tile.  A pure function of the arguments; everything else launches as before
+  if (!plan && !hist_rows && D == 128 && softcap == 0.0f && a.window == 0 && 32 % a.rep == 0 && T >= 32) {
+    constexpr int kRows = 32 * kWideWaves;
+    const int64_t n_wg = (M + kRows - 1) / kRows;
+    const int64_t nw = static_cast<int64_t>(n_groups) * Hkv * n_wg;
+    a.n_qg = static_cast<int32_t>(n_wg);
+    a.swizzle = (nw % 8 == 0 && nw >= 64) ? 1 : 0;
+    hipLaunchKernelGGL((prefix_attn_wide_kernel<128, kWideWaves>), dim3(static_cast<uint32_t>(nw)),
+                       dim3(64 * kWideWaves), 0, st, a);
+    return check_launch(name);
+  }
   const dim3 grid(static_cast<uint32_t>(nwg));
   const dim3 merge_grid(static_cast<uint32_t>(plan ? n_merge : 0));
 #define CS_ATTN_LAUNCH(DV)                                                              \
