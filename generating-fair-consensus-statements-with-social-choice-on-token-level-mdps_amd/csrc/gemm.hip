@@ -715,72 +715,90 @@ __global__ __launch_bounds__(64 * WAVES, 1) void thin_gemm_kernel(
   }
 }
 
-// thin variants: 5 = 16 features x 8 waves, 6 = 32 features x 8 waves, 7 = 16 features x
-// 16 waves (gated: one gate + one up tile, 8 / 8 / 16 waves)
+// ---- the host half: one variant table, one plan per call, one launcher ----
+
 constexpr int kThinMaxRows = 80;
-bool thin_variant(int variant) { return variant >= 5 && variant <= 7; }
-int thin_ft(int variant, int gated) { return gated || variant == 6 ? 2 : 1; }
-int thin_waves(int variant) { return variant == 7 ? 16 : 8; }
+enum GemmFamily { kFamWs, kFamWs2, kFamThin };   // ws_gemm_kernel, ws2_gemm_kernel, thin_gemm_kernel
 
-template <int MT, int FT, int GATED, int WAVES, int RING>
-void launch_thin(int blocks, hipStream_t st, const uint16_t* X, int64_t ldx, const uint16_t* W,
-                 int64_t ldw, uint16_t* Y, int64_t ldy, int64_t M, int64_t gate_off, int nsteps,
-                 int act) {
-  hipLaunchKernelGGL((thin_gemm_kernel<MT, FT, GATED, WAVES, RING>), dim3(blocks), dim3(64 * WAVES),
-                     0, st, X, ldx, W, ldw, Y, ldy, M, gate_off, nsteps, act);
+// What the `variant` argument 1..7 selects (0 = the library's choice, kGemmDefaultVariant).
+struct GemmVariant {
+  GemmFamily family;
+  int bn;          // W rows per workgroup
+  int nt;          // 16-column tiles per wave (ws2's NT, thin's FT)
+  int waves;
+  int ring;        // loads in flight per wave: the thin register ring's depth (ws, ws2: 3 stages)
+  int max_tiles;   // most 16-row tiles per workgroup
+  bool packed;     // takes a cs_gemm_pack'ed weight
+  bool split;      // takes a K split
+};
+constexpr GemmVariant kGemmVariants[] = {
+    // 1: ws, 2 row groups x 4 column groups of waves: 128 columns x up to 288 rows
+    {kFamWs, kGemmBN, 2, 8, 3, 2 * kGemmMaxMW, false, true},
+    // 2: ws2, the waves split only the columns: 8 waves x 32 columns
+    {kFamWs2, 256, 2, 8, 3, 18, true, true},
+    // 3: as 2 with 8 waves x 16 columns
+    {kFamWs2, 128, 1, 8, 3, 18, true, true},
+    // 4: as 2 with at most 9 row tiles (144 rows) per workgroup: the row blocks of a column
+    // tile pair on one XCD
+    {kFamWs2, 256, 2, 8, 3, 9, true, true},
+    // thin (M <= 80, no K split): 5 = 16 features x 8 waves, 6 = 32 features x 8 waves,
+    // 7 = 16 features x 16 waves
+    {kFamThin, 16, 1, 8, 3, kThinMaxRows / 16, false, false},
+    {kFamThin, 32, 2, 8, 3, kThinMaxRows / 16, false, false},
+    {kFamThin, 16, 1, 16, 2, kThinMaxRows / 16, false, false},
+};
+constexpr int kGemmVariantCount = sizeof(kGemmVariants) / sizeof(kGemmVariants[0]);
+constexpr int kGemmDefaultVariant = 2;
+
+// the variant that variant 1..7 runs: the 256-column ones need N % 256 == 0 and go to 3, or
+// to 1 when gated, without it
+constexpr int resolve_variant(int variant, int64_t N, bool gated) {
+  if (kGemmVariants[variant - 1].bn == 256 && N % 256) return gated ? 1 : 3;
+  return variant;
 }
 
-// row tiles 1..MAXMT (the caller keeps mt <= MAXMT)
-template <int FT, int GATED, int WAVES, int RING, int MAXMT>
-void dispatch_thin(int mt, int blocks, hipStream_t st, const uint16_t* X, int64_t ldx,
-                   const uint16_t* W, int64_t ldw, uint16_t* Y, int64_t ldy, int64_t M,
-                   int64_t gate_off, int nsteps, int act) {
-  if constexpr (MAXMT > 1) {
-    if (mt < MAXMT) {
-      dispatch_thin<FT, GATED, WAVES, RING, MAXMT - 1>(mt, blocks, st, X, ldx, W, ldw, Y, ldy, M,
-                                                       gate_off, nsteps, act);
-      return;
+// The row a call of the (resolved) variant runs: the table's, and where the gated forms
+// (W = gate|up rows, act(gate) * up out) differ from it, these differences.  M and N count
+// only through the three tests below: inst_form, which names an instantiation by its row
+// tiles and waves, and the N list of gemm_plans_are_launched must follow any new one.
+constexpr GemmVariant gemm_form(int variant, int64_t M, int64_t N, bool gated, bool packed) {
+  GemmVariant v = kGemmVariants[variant - 1];
+  if (!gated) return v;
+  if (v.family == kFamThin) {
+    v.bn = 32;      // one gate tile and its up tile: 16 features per workgroup
+    v.nt = 2;
+    if (v.waves == 16 && M > 3 * 16) {   // (16 gated waves spill at 4-5 row tiles: 8 waves there)
+      v.waves = 8;
+      v.ring = 3;
     }
+  } else if (variant == 3) {
+    v.nt = 2;       // 4 waves x 32 W rows: 64 features per workgroup, two workgroups per CU
+    v.waves = 4;
+  } else if (v.family == kFamWs2 && packed && M <= 80 && N % 224 == 0) {
+    // variants 2 and 4 on a packed weight at <= 80 rows (the per-rank decode steps): 7 waves
+    // x 32 W rows (112 features) per workgroup: the 70B gate|up (57,344 rows) is then 256
+    // workgroups on the 256 CUs instead of 224 (8 waves x 32 rows)
+    v.bn = 224;
+    v.waves = 7;
   }
-  launch_thin<MAXMT, FT, GATED, WAVES, RING>(blocks, st, X, ldx, W, ldw, Y, ldy, M, gate_off,
-                                             nsteps, act);
+  return v;
 }
 
-template <int MW, int GATED>
-void launch_ws(int blocks, hipStream_t st, const uint16_t* X, int64_t ldx, const uint16_t* W,
-               int64_t ldw, uint16_t* Y, int64_t ldy, float* P, int64_t M, int64_t n_out,
-               int64_t gate_off, int nk, int n_tiles, int splits, int act) {
-  hipLaunchKernelGGL((ws_gemm_kernel<MW, GATED>), dim3(blocks), dim3(kGemmThreads), 0, st, X, ldx, W,
-                     ldw, Y, ldy, P, M, n_out, gate_off, nk, n_tiles, splits, act);
-}
-
-template <int GATED>
-void dispatch_ws(int mw, int blocks, hipStream_t st, const uint16_t* X, int64_t ldx,
-                 const uint16_t* W, int64_t ldw, uint16_t* Y, int64_t ldy, float* P, int64_t M,
-                 int64_t n_out, int64_t gate_off, int nk, int n_tiles, int splits, int act) {
-#define CS_WS_CASE(V) \
-  case V: launch_ws<V, GATED>(blocks, st, X, ldx, W, ldw, Y, ldy, P, M, n_out, gate_off, nk, n_tiles, splits, act); break;
-  switch (mw) {
-    CS_WS_CASE(1) CS_WS_CASE(2) CS_WS_CASE(3) CS_WS_CASE(4) CS_WS_CASE(5)
-    CS_WS_CASE(6) CS_WS_CASE(7) CS_WS_CASE(8) CS_WS_CASE(9)
-    default: break;
-  }
-#undef CS_WS_CASE
-}
-
-// 16-row tiles per wave for M rows: all rows in one block up to 288
-int ws_mw(int64_t M) {
+// ws: 16-row tiles per wave (MW) for M rows: all rows in one block up to 288
+constexpr int ws_mw(int64_t M) {
   const int64_t tiles = (M + 15) / 16;
   const int64_t mw = (tiles + 1) / 2;
   return static_cast<int>(mw < kGemmMaxMW ? mw : kGemmMaxMW);
 }
 
-// ws2: row tiles per workgroup (instantiated counts) and row blocks for M rows. The 5-tile
-// block is taken on packed weights only (per-rank C5, 72 rows: 1-2% over 8 tiles there,
+// ws2: row tiles per workgroup (instantiated counts) and row blocks for `tiles` row tiles. The
+// 5-tile block is taken on packed weights only (per-rank C5, 72 rows: 1-2% over 8 tiles there,
 // profiles/r04af_ws2_mt5_ab.jsonl); on row-major weights it measured slower (gate|up 194 -> 224 us).
+// It never changes the row-block count: it is taken at 5 row tiles (one block either way) and,
+// with max_tiles 9, at 10 (two blocks either way), so cs_gemm_splits, which knows no
+// `packed`, picks the split of the packed form too (gemm_plans_are_launched checks it).
 constexpr int kWs2MT[] = {2, 4, 5, 8, 9, 12, 17, 18};
-void ws2_rows(int64_t M, int* mt, int64_t* mblocks, int max_tiles = 18, bool packed = false) {
-  const int64_t tiles = (M + 15) / 16;
+constexpr void ws2_rows(int64_t tiles, int max_tiles, bool packed, int* mt, int64_t* mblocks) {
   const int64_t mb = (tiles + max_tiles - 1) / max_tiles;
   const int64_t per = (tiles + mb - 1) / mb;
   int v = 18;
@@ -792,75 +810,167 @@ void ws2_rows(int64_t M, int* mt, int64_t* mblocks, int max_tiles = 18, bool pac
   *mblocks = (tiles + v - 1) / v;
 }
 
-template <int MT, int NT, int GATED, int WAVES, bool PACKED>
-void launch_ws2(int blocks, hipStream_t st, const uint16_t* X, int64_t ldx, const uint16_t* W,
-                int64_t ldw, uint16_t* Y, int64_t ldy, float* P, int64_t M, int64_t n_out,
-                int64_t gate_off, int nk, int n_tiles, int splits, int act, int m_blocks) {
-  hipLaunchKernelGGL((ws2_gemm_kernel<MT, NT, GATED, WAVES, PACKED>), dim3(blocks), dim3(64 * WAVES),
-                     0, st, X, ldx, W, ldw, Y, ldy, P, M, n_out, gate_off, nk, n_tiles, splits, act,
-                     m_blocks);
+// One launch: the instantiation and its arguments that do not depend on the operands' addresses.
+struct GemmPlan {
+  int variant, mt, gated, packed, waves;    // name the instantiation (inst_form); the variant
+                                            // as resolved, mt the row tiles (ws: MW)
+  int64_t grid;                             // 0: nothing to launch (M == 0)
+  int block;
+  int nk, n_tiles, splits, m_blocks;
+  int64_t n_out, gate_off;
+};
+
+// The form of the instantiation that (variant, row tiles, gated, packed, waves) names: gemm_form
+// at 16 * mt rows, with N a multiple of 224 for the 7-wave form alone.
+constexpr GemmVariant inst_form(int variant, int mt, int gated, int packed, int waves) {
+  return gemm_form(variant, 16 * mt, waves == 7 ? 7 * 256 : 256, gated, packed);
+}
+// Whether gemm_launch compiles that instantiation.  ws2 takes the row-tile counts of kWs2MT (the
+// 5-tile block on row-major weights too: no plan names it, its four kernels stay in the
+// library), ws and thin every count up to their most.
+constexpr bool gemm_compiled(const GemmVariant& v, int mt, int packed, int waves) {
+  bool listed = v.family != kFamWs2;
+  for (int c : kWs2MT) listed = listed || c == mt;
+  const int most = v.family == kFamWs ? v.max_tiles / 2 : v.max_tiles;   // (ws: two row groups)
+  return listed && mt >= 1 && mt <= most && v.waves == waves && (v.packed || !packed);
 }
 
-template <int NT, int GATED, int WAVES, bool PACKED>
-void dispatch_ws2(int mt, int blocks, hipStream_t st, const uint16_t* X, int64_t ldx,
-                  const uint16_t* W, int64_t ldw, uint16_t* Y, int64_t ldy, float* P, int64_t M,
-                  int64_t n_out, int64_t gate_off, int nk, int n_tiles, int splits, int act,
-                  int m_blocks) {
-#define CS_WS2_CASE(V)                                                                          \
-  case V:                                                                                       \
-    launch_ws2<V, NT, GATED, WAVES, PACKED>(blocks, st, X, ldx, W, ldw, Y, ldy, P, M, n_out,    \
-                                            gate_off, nk, n_tiles, splits, act, m_blocks);      \
-    break;
-  switch (mt) {
-    CS_WS2_CASE(2) CS_WS2_CASE(4) CS_WS2_CASE(5) CS_WS2_CASE(8) CS_WS2_CASE(9) CS_WS2_CASE(12)
-    CS_WS2_CASE(17)
-    CS_WS2_CASE(18)
-    default: break;
+// The plan of one cs_gemm_bf16 (packed: cs_gemm_bf16_packed) call with splits <= 0 resolved,
+// or the reason the call is rejected.  Pure host arithmetic: no allocation, no HIP call.
+constexpr const char* gemm_plan(GemmPlan* p, int64_t M, int64_t N, int64_t K, int splits, bool gated,
+                                int variant, bool packed) {
+  *p = GemmPlan{};
+  if (M < 0 || N <= 0 || K <= 0) return "bad shape";
+  if (variant == 0) variant = kGemmDefaultVariant;
+  const GemmVariant* row =
+      variant >= 1 && variant <= kGemmVariantCount ? &kGemmVariants[variant - 1] : nullptr;
+  if (packed) {
+    if (!row || !row->packed) return "variants 2-4 (the ws2 kernels) only";
+    if (K % kGemmBK) return "K must be a multiple of 64";
   }
-#undef CS_WS2_CASE
-}
-
-// W rows per workgroup of a variant (1: ws 128; 2: ws2 8 waves x 32; 3: ws2 8 x 16, gated
-// 4 x 32; 4: as 2 with at most 9 row tiles (144 rows) per workgroup)
-int64_t variant_bn(int variant, int gated) {
-  if (variant == 1) return 128;
-  if (variant == 3) return 128;
-  return 256;
-}
-
-int variant_max_tiles(int variant) { return variant == 4 ? 9 : 18; }
-
-int64_t gemm_tiles(int variant, int64_t M, int64_t N, int gated) {
-  if (variant == 1) {
-    const int mw = ws_mw(M);
-    return (gated ? N / 128 : N / kGemmBN) * ((M + 32 * mw - 1) / (32 * mw));
+  if (M == 0) return nullptr;
+  if (!row) return "variant must be 0..7";
+  if (N % 128) return "N must be a multiple of 128";
+  if (gated && splits > 1) return "the gated form takes no K split";
+  variant = resolve_variant(variant, N, gated);
+  const GemmVariant v = gemm_form(variant, M, N, gated, packed);
+  if (packed && !v.packed) return "N must be a multiple of 256 for this variant";
+  const int64_t tiles = (M + 15) / 16;
+  int mt = static_cast<int>(tiles);
+  int64_t mb = 1;
+  if (v.family == kFamWs) {
+    mt = ws_mw(M);
+    mb = (M + 32 * mt - 1) / (32 * mt);
+  } else if (v.family == kFamWs2) {
+    ws2_rows(tiles, v.max_tiles, packed, &mt, &mb);
+  } else if (tiles > v.max_tiles || K % kGemmBK || splits > 1) {
+    return "variants 5-7 take M <= 80, K % 64 == 0, no K split";
   }
-  int mt;
-  int64_t mb;
-  ws2_rows(M, &mt, &mb, variant_max_tiles(variant));
-  return (N / variant_bn(variant, gated)) * mb;
+  const int64_t n_tiles = N / v.bn;
+  int64_t s = splits;
+  if (s <= 0) {
+    s = 1;
+    // fill the 256 CUs (one 512-thread workgroup each) while keeping >= 8 K steps per split
+    while (v.split && !gated && n_tiles * mb * s < 256 && K % (kGemmBK * s * 2) == 0 &&
+           K / (kGemmBK * s * 2) >= 8)
+      s *= 2;
+  }
+  if (K % (kGemmBK * s)) return "K must be a multiple of 64 * splits";
+  // ws2 with more than one row block: the (column tile, split) cells are padded to groups of
+  // 8, which ws2_gemm_kernel deals to the row blocks of one XCD
+  const int64_t cells = n_tiles * s;
+  const int64_t grid = v.family == kFamWs2 && mb > 1 ? (cells + 7) / 8 * 8 * mb : cells * mb;
+  if (grid > 0x7fffffffLL) return "grid too large";
+  *p = GemmPlan{variant, mt, gated, packed, v.waves, grid, 64 * v.waves,
+                static_cast<int>(K / (kGemmBK * s)), static_cast<int>(n_tiles), static_cast<int>(s),
+                static_cast<int>(mb), gated ? N / 2 : N, gated ? N / 2 : 0};
+  return nullptr;
 }
 
-// grid of a ws2 launch: (column tile, split) cells padded to groups of 8 when row blocks pair
-int64_t ws2_grid(int64_t cells, int64_t mblocks) {
-  return mblocks > 1 ? (cells + 7) / 8 * 8 * mblocks : cells;
+// f(std::integral_constant<int, V>...) with each run-time v as the V of its list that equals
+// it: with_constants(f, Ints<...>{}, v, Ints<...>{}, v2, ...).  f returns bool; false, and f
+// is not called, when a v is in none of its list.
+template <int... Vs>
+using Ints = std::integer_sequence<int, Vs...>;
+template <int... Vs>
+constexpr bool has(Ints<Vs...>, int v) { return ((v == Vs) || ...); }
+template <typename F>
+bool with_constants(F&& f) { return f(); }
+template <typename F, int... Vs, typename... Rest>
+bool with_constants(F&& f, Ints<Vs...>, int v, Rest... rest) {
+  const auto bind = [&](auto c) { return with_constants([&](auto... cs) { return f(c, cs...); }, rest...); };
+  return ((v == Vs && bind(std::integral_constant<int, Vs>{})) || ...);
 }
 
-// the packed gated form at <= 80 rows (the per-rank decode steps) with 7 waves x 32 W rows
-// (112 features) per workgroup: the 70B gate|up (57,344 rows) is then 256 workgroups on
-// the 256 CUs instead of 224 (8 waves x 32 rows)
-bool ws2_gated7(int variant, int64_t M, int64_t N, int gated, bool packed) {
-  return gated && packed && (variant == 2 || variant == 4) && M <= 80 &&
-         N % 224 == 0;
+// the values gemm_launch takes for variant - 1, row tiles and waves
+using GemmVariantIds = std::make_integer_sequence<int, kGemmVariantCount>;
+using GemmTiles = std::make_integer_sequence<int, 2 * kGemmMaxMW + 1>;
+using GemmWaves = Ints<4, 7, 8, 16>;
+
+// Every plan names an instantiation gemm_launch compiles, and a packed weight never changes
+// the row-block count (ws2_rows).  The row tiles, N % 256, N % 224 and the 80-row bounds are
+// all a plan's instantiation depends on.
+constexpr bool gemm_plans_are_launched() {
+  for (int variant = 0; variant <= kGemmVariantCount; ++variant)
+    for (int gated = 0; gated <= 1; ++gated)
+      for (int64_t N : {128, 256, 1792})
+        for (int64_t tiles = 1; tiles <= 40; ++tiles) {
+          GemmPlan p[2] = {};
+          for (int packed = 0; packed <= 1; ++packed) {
+            GemmPlan& q = p[packed];
+            if (gemm_plan(&q, 16 * tiles, N, kGemmBK, 1, gated, variant, packed)) continue;
+            const GemmVariant v = inst_form(q.variant, q.mt, q.gated, q.packed, q.waves);
+            if (!gemm_compiled(v, q.mt, q.packed, q.waves) || !has(GemmTiles{}, q.mt) ||
+                !has(GemmWaves{}, q.waves) || 64 * v.waves != q.block)
+              return false;
+          }
+          if (p[0].grid && p[1].grid && p[0].m_blocks != p[1].m_blocks) return false;
+        }
+  return true;
+}
+static_assert(gemm_plans_are_launched(), "gemm_plan names an instantiation gemm_launch lacks");
+
+
+struct GemmArgs {
+  const uint16_t* x;
+  int64_t ldx;
+  const uint16_t* w;
+  int64_t ldw;
+  uint16_t* y;       // nullptr: the K split's partials are kept
+  int64_t ldy;
+  float* part;       // fp32 partials [splits][M][n_out] of a K split
+  int64_t M;
+  int act;
+};
+
+// Launches the plan's instantiation; false when it is not compiled (no plan of gemm_plan).
+bool gemm_launch(const GemmPlan& p, const GemmArgs& a, hipStream_t st) {
+  const dim3 grid(static_cast<uint32_t>(p.grid)), block(p.block);
+  float* part = p.splits > 1 ? a.part : nullptr;
+  const int act = p.gated ? a.act : 0;
+  return with_constants(
+      [&](auto id, auto mt, auto g, auto pk, auto wv) {
+        constexpr int MT = decltype(mt)::value, G = decltype(g)::value, PK = decltype(pk)::value,
+                      WV = decltype(wv)::value;
+        constexpr GemmVariant v = inst_form(decltype(id)::value + 1, MT, G, PK, WV);
+        constexpr bool compiled = gemm_compiled(v, MT, PK, WV);
+        if constexpr (compiled && v.family == kFamWs) {
+          hipLaunchKernelGGL((ws_gemm_kernel<MT, G>), grid, block, 0, st, a.x, a.ldx, a.w, a.ldw, a.y,
+                             a.ldy, part, a.M, p.n_out, p.gate_off, p.nk, p.n_tiles, p.splits, act);
+        } else if constexpr (compiled && v.family == kFamWs2) {
+          hipLaunchKernelGGL((ws2_gemm_kernel<MT, v.nt, G, WV, PK != 0>), grid, block, 0, st, a.x, a.ldx,
+                             a.w, a.ldw, a.y, a.ldy, part, a.M, p.n_out, p.gate_off, p.nk, p.n_tiles,
+                             p.splits, act, p.m_blocks);
+        } else if constexpr (compiled) {
+          hipLaunchKernelGGL((thin_gemm_kernel<MT, v.nt, G, WV, v.ring>), grid, block, 0, st, a.x, a.ldx,
+                             a.w, a.ldw, a.y, a.ldy, a.M, p.gate_off, p.nk, act);
+        }
+        return compiled;
+      },
+      GemmVariantIds{}, p.variant - 1, GemmTiles{}, p.mt, Ints<0, 1>{}, p.gated, Ints<0, 1>{}, p.packed,
+      GemmWaves{}, p.waves);
 }
 
-int resolve_variant(int variant, int64_t N, int gated) {
-  if (variant == 0) variant = 2;
-  if (thin_variant(variant)) return variant;
-  if ((variant == 2 || variant == 4) && N % 256) variant = gated ? 1 : 3;
-  if (variant == 3 && gated && N % 128) variant = 2;
-  return variant;
-}
 
 }  // namespace
 
@@ -868,156 +978,43 @@ extern "C" {
 
 int64_t cs_gemm_splits(int64_t M, int64_t N, int64_t K, int gated, int variant) {
   if (M <= 0 || N <= 0 || K <= 0 || N % 128) return 0;
-  if (gated || thin_variant(variant)) return 1;
-  variant = resolve_variant(variant, N, gated);
-  const int64_t tiles = gemm_tiles(variant, M, N, gated);
-  // fill the 256 CUs (one 512-thread workgroup each) while keeping >= 8 K steps per split
-  int64_t s = 1;
-  while (tiles * s < 256 && K % (kGemmBK * s * 2) == 0 && K / (kGemmBK * s * 2) >= 8) s *= 2;
-  return s;
+  GemmPlan p;     // (a call cs_gemm_bf16 rejects has no split)
+  return gemm_plan(&p, M, N, K, 0, gated != 0, variant, false) ? 1 : p.splits;
 }
 
 }  // extern "C"
 
 namespace {
 // cs_gemm_bf16 (packed = false) and cs_gemm_bf16_packed (W in cs_gemm_pack's layout: the ws2
-// variants 2-4 only, ldw = K)
-int gemm_impl(const void* x, int64_t ldx, const void* w, int64_t ldw, void* y, int64_t ldy,
-              int64_t M, int64_t N, int64_t K, int splits, int gated, int act, int variant,
-              float* workspace, cs_stream_t stream, bool packed) {
-  if (M < 0 || N <= 0 || K <= 0) return fail(CS_ERR_INVALID, "cs_gemm_bf16: bad shape");
-  if (packed) {
-    if (variant == 0) variant = 2;
-    if (variant < 2 || variant > 4)
-      return fail(CS_ERR_INVALID, "cs_gemm_bf16_packed: variants 2-4 (the ws2 kernels) only");
-    if (K % kGemmBK) return fail(CS_ERR_INVALID, "cs_gemm_bf16_packed: K must be a multiple of 64");
-    ldw = K;
-  }
-  if (M == 0) return CS_OK;
-  if (!x || !w) return fail(CS_ERR_INVALID, "cs_gemm_bf16: NULL pointer");
-  if (variant < 0 || variant > 7) return fail(CS_ERR_INVALID, "cs_gemm_bf16: variant must be 0..7");
-  if (N % 128) return fail(CS_ERR_INVALID, "cs_gemm_bf16: N must be a multiple of 128");
-  if (gated && splits > 1)
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: the gated form takes no K split");
-  variant = resolve_variant(variant, N, gated);
-  if (packed && variant != 2 && variant != 3 && variant != 4)
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16_packed: N must be a multiple of 256 for this variant");
-  if (splits <= 0) splits = static_cast<int>(cs_gemm_splits(M, N, K, gated, variant));
-  if (!y && (splits <= 1 || gated))
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: y may be NULL only with a K split (partials kept)");
-  if (K % (kGemmBK * splits))
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: K must be a multiple of 64 * splits");
-  if (ldx % 8 || ldw % 8 || (y && (ldy % 4 || ldy < (gated ? N / 2 : N))) || ldx < K || ldw < K)
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: leading dimensions too small or misaligned");
+// variants 2-4 only, ldw = K); fn is the entry point's name
+int gemm_impl(const char* fn, const void* x, int64_t ldx, const void* w, int64_t ldw, void* y,
+              int64_t ldy, int64_t M, int64_t N, int64_t K, int splits, int gated, int act,
+              int variant, float* workspace, cs_stream_t stream, bool packed) {
+  const auto bad = [fn](const char* why) { return fail(CS_ERR_INVALID, std::string(fn) + ": " + why); };
+  GemmPlan p;
+  if (const char* why = gemm_plan(&p, M, N, K, splits, gated != 0, variant, packed)) return bad(why);
+  if (p.grid == 0) return CS_OK;
+  if (!x || !w) return bad("NULL pointer");
+  if (!y && p.splits <= 1) return bad("y may be NULL only with a K split (partials kept)");
+  if (ldx % 8 || ldw % 8 || (y && (ldy % 4 || ldy < p.n_out)) || ldx < K || ldw < K)
+    return bad("leading dimensions too small or misaligned");
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15 ||
       reinterpret_cast<uintptr_t>(y) & 7)
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: operands must be 16-byte aligned (y 8-byte)");
-  if (splits > 1 && !workspace)
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: split K needs a workspace of splits * M * N floats");
+    return bad("operands must be 16-byte aligned (y 8-byte)");
+  if (p.splits > 1 && !workspace) return bad("split K needs a workspace of splits * M * N floats");
   // the split-K fold writes 16-byte vectors of 8 features at y + m * ldy + n
-  if (splits > 1 && y && (ldy % 8 || reinterpret_cast<uintptr_t>(y) & 15))
-    return fail(CS_ERR_INVALID, "cs_gemm_bf16: a K split needs y 16-byte aligned and ldy % 8 == 0");
-  if (thin_variant(variant)) {
-    if (M > kThinMaxRows || K % kGemmBK || splits > 1 || !y)
-      return fail(CS_ERR_INVALID, "cs_gemm_bf16: variants 5-7 take M <= 80, K % 64 == 0, no K split");
-    const int ft = thin_ft(variant, gated);
-    const int64_t n_out = gated ? N / 2 : N;
-    const int64_t blocks = gated ? n_out / 16 : n_out / (16 * ft);
-    const int mt = static_cast<int>((M + 15) / 16);
-    const int nsteps = static_cast<int>(K / kGemmBK);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t* X = static_cast<const uint16_t*>(x);
-    const uint16_t* Wp = static_cast<const uint16_t*>(w);
-    uint16_t* Y = static_cast<uint16_t*>(y);
-    const int b = static_cast<int>(blocks);
-    if (gated) {
-      if (variant == 7 && mt <= 3)    // (16 gated waves spill at 4-5 row tiles: 8 waves there)
-        dispatch_thin<2, 1, 16, 2, 3>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, M, n_out, nsteps, act);
-      else
-        dispatch_thin<2, 1, 8, 3, 5>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, M, n_out, nsteps, act);
-    } else if (variant == 5) {
-      dispatch_thin<1, 0, 8, 3, 5>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, M, 0, nsteps, 0);
-    } else if (variant == 6) {
-      dispatch_thin<2, 0, 8, 3, 5>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, M, 0, nsteps, 0);
-    } else {
-      dispatch_thin<1, 0, 16, 2, 5>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, M, 0, nsteps, 0);
-    }
-    return check_launch("cs_gemm_bf16");
-  }
-  const int64_t tiles = gemm_tiles(variant, M, N, gated);
-  const int64_t blocks = tiles * splits;
-  if (blocks > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_gemm_bf16: grid too large");
-  const int nk = static_cast<int>(K / (kGemmBK * splits));
+  if (p.splits > 1 && y && (ldy % 8 || reinterpret_cast<uintptr_t>(y) & 15))
+    return bad("a K split needs y 16-byte aligned and ldy % 8 == 0");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint16_t* X = static_cast<const uint16_t*>(x);
-  const uint16_t* Wp = static_cast<const uint16_t*>(w);
-  uint16_t* Y = static_cast<uint16_t*>(y);
-  float* Pp = splits > 1 ? workspace : nullptr;
-  if (variant == 1) {
-    const int mw = ws_mw(M);
-    const int n_tiles = static_cast<int>(gated ? N / 128 : N / kGemmBN);
-    if (gated)
-      dispatch_ws<1>(mw, static_cast<int>(blocks), st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2,
-                     N / 2, nk, n_tiles, 1, act);
-    else
-      dispatch_ws<0>(mw, static_cast<int>(blocks), st, X, ldx, Wp, ldw, Y, ldy, Pp, M, N, 0, nk,
-                     n_tiles, splits, 0);
-  } else {
-    int mt;
-    int64_t mb;
-    ws2_rows(M, &mt, &mb, variant_max_tiles(variant), packed);
-    const int n_tiles = static_cast<int>(N / variant_bn(variant, gated));
-    const int64_t grid = ws2_grid(static_cast<int64_t>(n_tiles) * splits, mb);
-    if (grid > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_gemm_bf16: grid too large");
-    const int b = static_cast<int>(grid);
-    const int mbi = static_cast<int>(mb);
-    if (ws2_gated7(variant, M, N, gated, packed)) {
-      const int n7 = static_cast<int>(N / 224);     // (M <= 80: one row block, mt <= 5)
-      if (mt == 2)
-        launch_ws2<2, 2, 1, 7, true>(n7, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                     n7, 1, act, 1);
-      else if (mt == 4)
-        launch_ws2<4, 2, 1, 7, true>(n7, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                     n7, 1, act, 1);
-      else
-        launch_ws2<5, 2, 1, 7, true>(n7, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                     n7, 1, act, 1);
-    } else if (gated && variant == 3) {
-      if (packed)
-        dispatch_ws2<2, 1, 4, true>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                    n_tiles, 1, act, mbi);
-      else
-        dispatch_ws2<2, 1, 4, false>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                     n_tiles, 1, act, mbi);
-    } else if (gated) {
-      if (packed)
-        dispatch_ws2<2, 1, 8, true>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                    n_tiles, 1, act, mbi);
-      else
-        dispatch_ws2<2, 1, 8, false>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, nullptr, M, N / 2, N / 2, nk,
-                                     n_tiles, 1, act, mbi);
-    } else if (variant == 3) {
-      if (packed)
-        dispatch_ws2<1, 0, 8, true>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, Pp, M, N, 0, nk, n_tiles, splits,
-                                    0, mbi);
-      else
-        dispatch_ws2<1, 0, 8, false>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, Pp, M, N, 0, nk, n_tiles,
-                                     splits, 0, mbi);
-    } else {
-      if (packed)
-        dispatch_ws2<2, 0, 8, true>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, Pp, M, N, 0, nk, n_tiles, splits,
-                                    0, mbi);
-      else
-        dispatch_ws2<2, 0, 8, false>(mt, b, st, X, ldx, Wp, ldw, Y, ldy, Pp, M, N, 0, nk, n_tiles,
-                                     splits, 0, mbi);
-    }
-  }
-  if (splits > 1 && !gated && Y) {     // y == NULL: the caller folds the partials itself
+  const GemmArgs a{static_cast<const uint16_t*>(x), ldx, static_cast<const uint16_t*>(w), ldw,
+                   static_cast<uint16_t*>(y), ldy, workspace, M, act};
+  if (!gemm_launch(p, a, st)) return bad("no kernel is compiled for this plan");
+  if (p.splits > 1 && a.y) {   // y == NULL: the caller folds the partials itself
     const int64_t nv = M * (N / 8);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(static_cast<uint32_t>((nv + 255) / 256)), dim3(256),
-                       0, st, workspace, splits, M, N, Y, ldy);
+                       0, st, workspace, p.splits, M, N, a.y, ldy);
   }
-  return check_launch("cs_gemm_bf16");
+  return check_launch(fn);
 }
 
 // Wp[((T * ns + s) * 2 + h) * 512 + 8 l + e] = W[16 T + l % 16][64 s + 32 h + 8 (l / 16) + e]
@@ -1042,15 +1039,15 @@ extern "C" {
 int cs_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, void* y, int64_t ldy,
                  int64_t M, int64_t N, int64_t K, int splits, int gated, int act, int variant,
                  float* workspace, cs_stream_t stream) {
-  return gemm_impl(x, ldx, w, ldw, y, ldy, M, N, K, splits, gated, act, variant, workspace, stream,
-                   false);
+  return gemm_impl("cs_gemm_bf16", x, ldx, w, ldw, y, ldy, M, N, K, splits, gated, act, variant,
+                   workspace, stream, false);
 }
 
 int cs_gemm_bf16_packed(const void* x, int64_t ldx, const void* w_packed, void* y, int64_t ldy,
                         int64_t M, int64_t N, int64_t K, int splits, int gated, int act,
                         int variant, float* workspace, cs_stream_t stream) {
-  return gemm_impl(x, ldx, w_packed, K, y, ldy, M, N, K, splits, gated, act, variant, workspace,
-                   stream, true);
+  return gemm_impl("cs_gemm_bf16_packed", x, ldx, w_packed, K, y, ldy, M, N, K, splits, gated, act,
+                   variant, workspace, stream, true);
 }
 
 int cs_gemm_pack(const void* w, int64_t ldw, int64_t N, int64_t K, void* w_packed,

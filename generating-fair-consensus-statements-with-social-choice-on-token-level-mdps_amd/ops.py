@@ -945,6 +945,9 @@ def _add_rms_norm_splitk(L, a, lda, weight, eps, part, b_weight, plus_one, s_out
     return out
 
 
+_ACT = {"silu": 0, "gelu_tanh": 1}      # the `act` argument of cs_gated_act and cs_gemm_bf16
+
+
 def gated_act(gate: torch.Tensor, up: torch.Tensor, act: str = "silu",
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(gate) * up (cs_gated_act): SiLU (Llama-3) or tanh-GeLU (Gemma-2); [rows, F] bf16."""
@@ -958,8 +961,8 @@ def gated_act(gate: torch.Tensor, up: torch.Tensor, act: str = "silu",
         out = torch.empty(rows, F, dtype=torch.bfloat16, device=gate.device)
     ldo = _rows2d(out, "out")
     _require_cuda(gate, up, out)
-    rc = L.cs_gated_act(gate.data_ptr(), ldg, up.data_ptr(), ldu, rows, F,
-                        {"silu": 0, "gelu_tanh": 1}[act], out.data_ptr(), ldo, _stream())
+    rc = L.cs_gated_act(gate.data_ptr(), ldg, up.data_ptr(), ldu, rows, F, _ACT[act],
+                        out.data_ptr(), ldo, _stream())
     _lib.check(rc, "cs_gated_act")
     return out
 
@@ -1029,16 +1032,19 @@ def linear(x: torch.Tensor, w: torch.Tensor, *, gated: bool = False, act: str = 
     add_rms_norm to fold); every other path returns the bf16 tensor as usual."""
     if x.is_cuda and x.dim() == 2:
         ch = gemm_choice(x.shape[0], w.shape[0], w.shape[1], gated, packed=packed is not None)
-        if ch is not None and ch["packed"] and gemm_ok(x, w, gated):
-            if not fold and not gated and out is None and ch["splits"] > 1:
-                return gemm_packed_partials(x, packed, splits=ch["splits"], variant=ch["variant"])
-            return gemm_packed(x, packed, gated=gated, act=act, splits=ch["splits"],
-                               variant=ch["variant"], out=out)
-        if ch is not None and gemm_ok(x, w, gated):
-            if not fold and not gated and out is None and int(ch["splits"]) > 1:
-                return gemm_partials(x, w, splits=int(ch["splits"]), variant=int(ch["variant"]))
-            return gemm(x, w, gated=gated, act=act, splits=int(ch["splits"]),
-                        variant=int(ch["variant"]), out=out)
+        if ch is not None:
+            # through the public names (a test counts the calls by replacing them); their
+            # body checks the operands, once per call, and what it refuses goes to hipBLASLt
+            wt = packed if ch["packed"] else w
+            try:
+                if not fold and not gated and out is None and ch["splits"] > 1:
+                    part = gemm_packed_partials if ch["packed"] else gemm_partials
+                    return part(x, wt, splits=ch["splits"], variant=ch["variant"])
+                run = gemm_packed if ch["packed"] else gemm
+                return run(x, wt, gated=gated, act=act, splits=ch["splits"], variant=ch["variant"],
+                           out=out)
+            except _OperandsRefused:
+                pass
     if gated:          # the plain GEMM (on whichever form is faster) + cs_gated_act
         F = w.shape[0] // 2
         y = linear(x, w, packed=packed)
@@ -1062,56 +1068,6 @@ def linear_into_residual(x: torch.Tensor, w: torch.Tensor, h: torch.Tensor, *,
         return False
     h.addmm_(x, w.t())
     return True
-
-
-def gemm_ok(x: torch.Tensor, w: torch.Tensor, gated: bool = False) -> bool:
-    """Whether cs_gemm_bf16 takes y = x @ w.T: bf16 2-D operands with unit column stride,
-    N a multiple of 128, K of 64, 16-byte aligned rows."""
-    if x.dim() != 2 or w.dim() != 2 or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
-        return False
-    N, K = w.shape
-    if x.shape[1] != K or N % 128 or K % 64 or x.stride(1) != 1 or w.stride(1) != 1:
-        return False
-    if (x.stride(0) % 8 and x.shape[0] > 1) or w.stride(0) % 8:
-        return False
-    return x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
-
-
-def gemm(x: torch.Tensor, w: torch.Tensor, *, gated: bool = False, act: str = "silu",
-         splits: int = 0, variant: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x @ w.T (cs_gemm_bf16): x [M, K], w [N, K] bf16, y [M, N] bf16, fp32 accumulation.
-    gated: w is the fused gate|up weight [2F, K] and y [M, F] = act(gate) * up (the rounding
-    of cs_gated_act).  splits: K split (0 = the library's choice); the fp32 partials are a
-    per-call tensor (inside a capture it belongs to the graph's pool)."""
-    L = _lib.load()
-    if not gemm_ok(x, w, gated):
-        raise CSError("cs_gemm_bf16 needs bf16 x [M, K], w [N, K] with N % 128 == 0, K % 64 == 0")
-    M, K = x.shape
-    N = w.shape[0]
-    n_out = N // 2 if gated else N
-    if out is None:
-        out = torch.empty(M, n_out, dtype=torch.bfloat16, device=x.device)
-    if out.shape != (M, n_out) or out.dtype != torch.bfloat16 or out.stride(1) != 1:
-        raise CSError("out must be a bf16 [M, N] tensor with unit column stride")
-    _require_cuda(x, w, out)
-    if gated:
-        splits = 1
-    elif splits <= 0:
-        splits = int(L.cs_gemm_splits(M, N, K, 0, variant))
-    part = (torch.empty(splits * M * N, dtype=torch.float32, device=x.device)
-            if splits > 1 else None)
-    ldx = x.stride(0) if M > 1 else K
-    ldy = out.stride(0) if M > 1 else n_out
-    if splits > 1 and (ldy % 8 or out.data_ptr() % 16):
-        # the split-K fold stores 16-byte vectors: fold into an aligned tensor, then copy
-        tmp = gemm(x, w, splits=splits, variant=variant)
-        out.copy_(tmp)
-        return out
-    rc = L.cs_gemm_bf16(x.data_ptr(), ldx, w.data_ptr(), w.stride(0), out.data_ptr(), ldy, M, N,
-                        K, splits, int(bool(gated)), {"silu": 0, "gelu_tanh": 1}[act], variant,
-                        part.data_ptr() if part is not None else None, _stream())
-    _lib.check(rc, "cs_gemm_bf16")
-    return out
 
 
 class PackedWeight:
@@ -1140,70 +1096,98 @@ def gemm_pack(w: torch.Tensor) -> PackedWeight:
     return PackedWeight(out, N, K)
 
 
-def gemm_packed(x: torch.Tensor, pw: PackedWeight, *, gated: bool = False, act: str = "silu",
-                splits: int = 0, variant: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """ops.gemm on a packed weight (cs_gemm_bf16_packed, variants 0 / 2 / 3 / 4): bitwise the
-    unpacked result."""
+class _OperandsRefused(CSError):
+    """Operands cs_gemm_bf16 does not take (gemm_ok): ``linear`` then runs hipBLASLt."""
+
+
+def _gemm_operands(x: torch.Tensor, w: "torch.Tensor | PackedWeight"):
+    """(the weight's tensor, its row stride, N, K) when cs_gemm_bf16 takes y = x @ w.T (see
+    gemm_ok), else None."""
+    packed = isinstance(w, PackedWeight)
+    wt = w.data if packed else w
+    if x.dim() != 2 or wt.dim() != (1 if packed else 2):
+        return None
+    if x.dtype != torch.bfloat16 or wt.dtype != torch.bfloat16:
+        return None
+    (M, Kx), (ldx, col_x) = x.shape, x.stride()
+    (N, K), (ldw, col_w) = ((w.N, w.K), (w.K, 1)) if packed else (wt.shape, wt.stride())
+    if Kx != K or N % 128 or K % 64 or col_x != 1 or col_w != 1 or (ldx % 8 and M > 1) or ldw % 8:
+        return None
+    return (wt, ldw, N, K) if x.data_ptr() % 16 == 0 and wt.data_ptr() % 16 == 0 else None
+
+
+def gemm_ok(x: torch.Tensor, w: "torch.Tensor | PackedWeight", gated: bool = False) -> bool:
+    """Whether cs_gemm_bf16 takes y = x @ w.T: bf16 2-D operands with unit column stride,
+    N a multiple of 128, K of 64, 16-byte aligned rows (a PackedWeight: its K-long rows)."""
+    return _gemm_operands(x, w) is not None
+
+
+def _gemm(who: str, x: torch.Tensor, w: "torch.Tensor | PackedWeight", gated: bool = False,
+          act: str = "silu", splits: int = 0, variant: int = 0, out: Optional[torch.Tensor] = None,
+          partials: bool = False):
+    """The body of gemm, gemm_packed, gemm_partials and gemm_packed_partials: cs_gemm_bf16 on
+    a tensor w, cs_gemm_bf16_packed on a PackedWeight; the bf16 result, or (partials, y =
+    NULL) the K split's unfolded SplitPartials."""
     L = _lib.load()
-    M, K = x.shape
-    N = pw.N
-    if x.dtype != torch.bfloat16 or x.stride(1) != 1 or K != pw.K:
-        raise CSError("gemm_packed needs bf16 x [M, K] matching the packed weight")
+    operands = _gemm_operands(x, w)
+    if operands is None:
+        raise _OperandsRefused(f"{who} needs bf16 x [M, K], w [N, K] with N % 128 == 0, K % 64 == 0")
+    if partials and splits < 2:
+        raise CSError(f"{who} needs splits >= 2")
+    wt, ldw, N, K = operands
+    packed = wt is not w
+    M = x.shape[0]
     n_out = N // 2 if gated else N
-    if out is None:
+    if out is None and not partials:
         out = torch.empty(M, n_out, dtype=torch.bfloat16, device=x.device)
-    if out.shape != (M, n_out) or out.dtype != torch.bfloat16 or out.stride(1) != 1:
+    if out is not None and (out.shape != (M, n_out) or out.dtype != torch.bfloat16 or out.stride(1) != 1):
         raise CSError("out must be a bf16 [M, N] tensor with unit column stride")
-    _require_cuda(x, pw.data, out)
+    _require_cuda(x, wt, out)
     if gated:
         splits = 1
     elif splits <= 0:
         splits = int(L.cs_gemm_splits(M, N, K, 0, variant))
     ldx = x.stride(0) if M > 1 else K
-    ldy = out.stride(0) if M > 1 else n_out
-    if splits > 1 and (ldy % 8 or out.data_ptr() % 16):
-        out.copy_(gemm_packed(x, pw, splits=splits, variant=variant))
+    ldy = 0 if out is None else out.stride(0) if M > 1 else n_out
+    if out is not None and splits > 1 and (ldy % 8 or out.data_ptr() % 16):
+        # the split-K fold stores 16-byte vectors: fold into an aligned tensor, then copy
+        out.copy_(_gemm(who, x, w, splits=splits, variant=variant))
         return out
-    part = (torch.empty(splits * M * N, dtype=torch.float32, device=x.device)
-            if splits > 1 else None)
-    rc = L.cs_gemm_bf16_packed(x.data_ptr(), ldx, pw.data.data_ptr(), out.data_ptr(), ldy, M, N,
-                               K, splits, int(bool(gated)), {"silu": 0, "gelu_tanh": 1}[act],
-                               variant, part.data_ptr() if part is not None else None, _stream())
-    _lib.check(rc, "cs_gemm_bf16_packed")
-    return out
+    part = torch.empty(splits, M, N, dtype=torch.float32, device=x.device) if splits > 1 else None
+    ws = (wt.data_ptr(),) if packed else (wt.data_ptr(), ldw)
+    entry = L.cs_gemm_bf16_packed if packed else L.cs_gemm_bf16
+    rc = entry(x.data_ptr(), ldx, *ws, None if out is None else out.data_ptr(), ldy, M, N, K, splits,
+               int(bool(gated)), _ACT[act], variant, None if part is None else part.data_ptr(),
+               _stream())
+    _lib.check(rc, "cs_gemm_bf16_packed" if packed else "cs_gemm_bf16")
+    return SplitPartials(part) if partials else out
+
+
+def gemm(x: torch.Tensor, w: torch.Tensor, *, gated: bool = False, act: str = "silu",
+         splits: int = 0, variant: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x @ w.T (cs_gemm_bf16): x [M, K], w [N, K] bf16, y [M, N] bf16, fp32 accumulation.
+    gated: w is the fused gate|up weight [2F, K] and y [M, F] = act(gate) * up (the rounding
+    of cs_gated_act).  splits: K split (0 = the library's choice); the fp32 partials are a
+    per-call tensor (inside a capture it belongs to the graph's pool)."""
+    return _gemm("cs_gemm_bf16", x, w, gated, act, splits, variant, out)
+
+
+def gemm_packed(x: torch.Tensor, pw: PackedWeight, *, gated: bool = False, act: str = "silu",
+                splits: int = 0, variant: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.gemm on a packed weight (cs_gemm_bf16_packed, variants 0 / 2 / 3 / 4): bitwise the
+    unpacked result."""
+    return _gemm("gemm_packed", x, pw, gated, act, splits, variant, out)
 
 
 def gemm_packed_partials(x: torch.Tensor, pw: PackedWeight, *, splits: int,
                          variant: int = 0) -> SplitPartials:
     """gemm_partials on a packed weight (cs_gemm_bf16_packed with y = NULL)."""
-    L = _lib.load()
-    M, K = x.shape
-    N = pw.N
-    if x.dtype != torch.bfloat16 or x.stride(1) != 1 or K != pw.K or splits < 2:
-        raise CSError("gemm_packed_partials needs bf16 x [M, K] matching the weight, splits >= 2")
-    _require_cuda(x, pw.data)
-    part = torch.empty(splits, M, N, dtype=torch.float32, device=x.device)
-    ldx = x.stride(0) if M > 1 else K
-    rc = L.cs_gemm_bf16_packed(x.data_ptr(), ldx, pw.data.data_ptr(), None, 0, M, N, K, splits, 0,
-                               0, variant, part.data_ptr(), _stream())
-    _lib.check(rc, "cs_gemm_bf16_packed")
-    return SplitPartials(part)
+    return _gemm("gemm_packed_partials", x, pw, splits=splits, variant=variant, partials=True)
 
 
 def gemm_partials(x: torch.Tensor, w: torch.Tensor, *, splits: int, variant: int = 0) -> SplitPartials:
     """The fp32 partials [splits, M, N] of cs_gemm_bf16 with a K split, unfolded (y = NULL)."""
-    L = _lib.load()
-    if not gemm_ok(x, w) or splits < 2:
-        raise CSError("gemm_partials needs cs_gemm_bf16 operands and splits >= 2")
-    M, K = x.shape
-    N = w.shape[0]
-    _require_cuda(x, w)
-    part = torch.empty(splits, M, N, dtype=torch.float32, device=x.device)
-    ldx = x.stride(0) if M > 1 else K
-    rc = L.cs_gemm_bf16(x.data_ptr(), ldx, w.data_ptr(), w.stride(0), None, 0, M, N, K, splits, 0,
-                        0, variant, part.data_ptr(), _stream())
-    _lib.check(rc, "cs_gemm_bf16")
-    return SplitPartials(part)
+    return _gemm("gemm_partials", x, w, splits=splits, variant=variant, partials=True)
 
 
 def hist_rows_update(src_rows: torch.Tensor, dst_rows: torch.Tensor, parent: torch.Tensor,

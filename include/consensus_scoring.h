@@ -590,7 +590,9 @@ int cs_gated_act(const void* gate, int64_t ld_gate, const void* up, int64_t ld_u
  * CU; N a multiple of 128), 4 = as 2 with at most 144 rows per workgroup (row blocks of a
  * column tile paired on one XCD); 5-7 = the thin form for M <= 80 (no K split: every wave
  * of a workgroup streams its own K slice into registers, no barrier until the final fold;
- * 5: 16 features x 8 waves, 6: 32 x 8, 7: 16 x 16).  N a multiple of 128, K of 64 * splits;
+ * 5: 16 features x 8 waves, 6: 32 x 8, 7: 16 x 16).  The variants' tile shapes, with what the
+ * gated forms change, are the table kGemmVariants and gemm_form beside it in csrc/gemm.hip;
+ * N % 256 != 0 sends variants 2 and 4 to 3 (gated: to 1).  N a multiple of 128, K of 64 * splits;
  * ldx, ldw multiples of 8, ldy of 4; X, W 16-byte aligned.  Deterministic (no atomics).
  *
  * Replaces: part of the remote forward behind every get_prompt_logprobs call
@@ -601,7 +603,9 @@ int cs_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, void* y
                  int64_t M, int64_t N, int64_t K, int splits, int gated, int act, int variant,
                  float* workspace, cs_stream_t stream);
 
-/* cs_gemm_splits — the K split cs_gemm_bf16 takes for splits <= 0 (>= 1; 0 on a bad shape). */
+/* cs_gemm_splits — the K split cs_gemm_bf16 takes for splits <= 0 (>= 1; 0 on a bad shape:
+ * M, N or K <= 0, or N % 128 != 0).  1 for every other call that cs_gemm_bf16 rejects: a
+ * variant outside 0..7, K % 64 != 0, a thin variant with M > 80. */
 int64_t cs_gemm_splits(int64_t M, int64_t N, int64_t K, int gated, int variant);
 
 /*

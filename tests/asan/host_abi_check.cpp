@@ -157,6 +157,22 @@ static void check_planners(std::mt19937_64& rng, int iters) {
       }
   }
   CHECK(cs_gemm_splits(8, 100, 64, 0, 2) == 0, "N %% 128 accepted");
+  // every variant and row-tile count through the plan: N = 384 takes the N % 256 fallback,
+  // 1792 = 8 x 224 is the 7-wave form's; a split divides K into whole 64-steps, a power of
+  // two of them, and never leaves fewer than 8
+  for (int variant = 0; variant <= 7; ++variant)
+    for (int64_t N : {128, 256, 384, 1792})
+      for (int64_t Kd : {64, 1024, 1344, 14336, 1 << 20})
+        for (int64_t M = 1; M <= 600; ++M)
+          for (int gated = 0; gated <= 1; ++gated) {
+            const int64_t s = cs_gemm_splits(M, N, Kd, gated, variant);
+            CHECK(s >= 1 && (s & (s - 1)) == 0 && Kd % (64 * s) == 0 && (s == 1 || Kd / (64 * s) >= 8),
+                  "cs_gemm_splits(%lld, %lld, %lld, %d, %d) = %lld", (long long)M, (long long)N,
+                  (long long)Kd, gated, variant, (long long)s);
+            if (gated || variant >= 5) CHECK(s == 1, "a gated / thin GEMM split %lld", (long long)s);
+            if (N == 384 && (variant == 2 || variant == 4))
+              CHECK(s == cs_gemm_splits(M, N, Kd, gated, 3), "N %% 256 != 0 did not go to variant 3");
+          }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -233,6 +249,17 @@ static void check_rejections() {
   REJECTS(cs_gemm_bf16(nullptr, 64, d, 64, d, 128, 4, 128, 64, 1, 0, 0, 2, nullptr, nullptr));
   REJECTS(cs_gemm_bf16(d, 64, d, 64, d, 128, 81, 128, 64, 1, 0, 0, 5, nullptr, nullptr));
   REJECTS(cs_gemm_bf16_packed(d, 64, d, d, 128, 4, 128, 64, 1, 0, 0, 5, nullptr, nullptr));
+  REJECTS(cs_gemm_bf16_packed(d, 64, d, d, 128, 4, 128, 64, 1, 0, 0, 1, nullptr, nullptr));   // ws2 variants only
+  REJECTS(cs_gemm_bf16(d, 64, d, 64, d, 128, 8, 128, 64, 1, 0, 0, 8, nullptr, nullptr));      // variant 8
+  REJECTS(cs_gemm_bf16(d, 128, d, 128, d, 128, 8, 128, 128, 2, 0, 0, 6, f, nullptr));         // thin with a K split
+  // packed, gated, N % 256 != 0: variant 2 goes to 1, which takes no packed weight
+  REJECTS(cs_gemm_bf16_packed(d, 64, d, d, 192, 4, 384, 64, 1, 1, 0, 2, nullptr, nullptr));
+  // a message names the entry point that was called; an empty call is no error
+  REJECTS(cs_gemm_bf16_packed(d, 64, d, d, 128, 4, 100, 64, 1, 0, 0, 2, nullptr, nullptr));
+  CHECK(std::strncmp(cs_last_error(), "cs_gemm_bf16_packed: ", 21) == 0, "names %s", cs_last_error());
+  REJECTS(cs_gemm_bf16(d, 64, d, 64, d, 128, 4, 100, 64, 1, 0, 0, 2, nullptr, nullptr));
+  CHECK(std::strncmp(cs_last_error(), "cs_gemm_bf16: ", 14) == 0, "names %s", cs_last_error());
+  CHECK(cs_gemm_bf16(d, 64, d, 64, d, 128, 0, 128, 64, 1, 0, 0, 2, nullptr, nullptr) == 0, "empty gemm");
   REJECTS(cs_gemm_pack(d, 64, 24, 64, d, nullptr));
   REJECTS(cs_gemm_pack(reinterpret_cast<void*>(uintptr_t{260}), 64, 32, 64, d, nullptr));
   REJECTS(cs_add_rms_norm(nullptr, 64, nullptr, 0, nullptr, d, 64, d, 4, 64, 1e-6f, 0, d, 64, nullptr));

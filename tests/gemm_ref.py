@@ -192,21 +192,19 @@ def selector_decode(wi, got, want, M, K, shift, limit=6):
 
 WS2_MT = (2, 4, 5, 8, 9, 12, 17, 18)     # kWs2MT
 WS_MAX_MW = 9                            # kGemmMaxMW
+# kGemmVariants: variant -> (family, W rows per workgroup, most row tiles per workgroup)
+VARIANTS = {1: ("ws", 128, 18), 2: ("ws2", 256, 18), 3: ("ws2", 128, 18), 4: ("ws2", 256, 9),
+            5: ("thin", 16, 5), 6: ("thin", 32, 5), 7: ("thin", 16, 5)}
 
 
 def thin_variant(variant):
-    return 5 <= variant <= 7
+    return VARIANTS.get(variant or 2, ("",))[0] == "thin"
 
 
 def resolve_variant(variant, N, gated):
-    if variant == 0:
-        variant = 2
-    if thin_variant(variant):
-        return variant
-    if variant in (2, 4) and N % 256:
-        variant = 1 if gated else 3
-    if variant == 3 and gated and N % 128:
-        variant = 2
+    variant = variant or 2
+    if VARIANTS[variant][1] == 256 and N % 256:
+        return 1 if gated else 3
     return variant
 
 
@@ -224,38 +222,26 @@ def ws2_rows(M, max_tiles=18, packed=False):
     return mt, (tiles + mt - 1) // mt
 
 
-def variant_bn(variant, gated):
-    return 128 if variant in (1, 3) else 256
-
-
-def variant_max_tiles(variant):
-    return 9 if variant == 4 else 18
-
-
-def gemm_tiles(variant, M, N, gated):
+def gemm_tiles(variant, M, N):
+    """workgroups per K split: column tiles x row blocks (the same on a packed weight)"""
+    _, bn, max_tiles = VARIANTS[variant]
     if variant == 1:
         mw = ws_mw(M)
-        return (N // 128) * ((M + 32 * mw - 1) // (32 * mw))
-    _, mb = ws2_rows(M, variant_max_tiles(variant))        # (never packed: as cs_gemm_splits)
-    return (N // variant_bn(variant, gated)) * mb
+        return (N // bn) * ((M + 32 * mw - 1) // (32 * mw))
+    return (N // bn) * ws2_rows(M, max_tiles)[1]
 
 
 def ws2_grid(cells, mblocks):
     return (cells + 7) // 8 * 8 * mblocks if mblocks > 1 else cells
 
 
-def ws2_gated7(variant, M, N, gated, packed):
-    return bool(gated and packed and variant in (2, 4) and M <= 80 and N % 224 == 0)
-
-
 def gemm_splits(M, N, K, gated, variant):
-    """cs_gemm_splits"""
+    """cs_gemm_splits (1 for a call cs_gemm_bf16 rejects: here a variant outside 0..7)"""
     if M <= 0 or N <= 0 or K <= 0 or N % 128:
         return 0
-    if gated or thin_variant(variant):
+    if gated or thin_variant(variant) or (variant or 2) not in VARIANTS:
         return 1
-    variant = resolve_variant(variant, N, gated)
-    tiles = gemm_tiles(variant, M, N, gated)
+    tiles = gemm_tiles(resolve_variant(variant, N, gated), M, N)
     s = 1
     while tiles * s < 256 and K % (BK * s * 2) == 0 and K // (BK * s * 2) >= 8:
         s *= 2
@@ -268,18 +254,19 @@ def thin_slices(nsteps, waves):
 
 
 def launch(variant, M, N, K, gated=False, packed=False, splits=1):
-    """What one cs_gemm_bf16(_packed) call launches: {"name": the template instantiation,
-    "nk", "splits", "grid"} and, thin, "waves", "ring", "slices"."""
+    """What one cs_gemm_bf16(_packed) call launches (gemm_plan): {"name": the template
+    instantiation, "nk", "splits", "grid"} and, thin, "waves", "ring", "slices"."""
     gated, packed = int(bool(gated)), bool(packed)
-    variant = resolve_variant(2 if packed and variant == 0 else variant, N, gated)
-    assert N % 128 == 0 and K % BK == 0 and not (packed and variant not in (2, 3, 4))
+    variant = resolve_variant(variant, N, gated)
+    family, bn, max_tiles = VARIANTS[variant]
+    assert N % 128 == 0 and K % BK == 0 and not (packed and family != "ws2")
     if splits <= 0:
         splits = gemm_splits(M, N, K, gated, variant)
     assert K % (BK * splits) == 0 and not (gated and splits > 1)
-    if thin_variant(variant):
+    if family == "thin":
         assert M <= THIN_MAX_ROWS and splits == 1
         mt = (M + 15) // 16
-        if gated:
+        if gated:         # gemm_form: one gate + one up tile; 16 waves up to 3 row tiles
             ft, waves, ring = (2, 16, 2) if variant == 7 and mt <= 3 else (2, 8, 3)
         else:
             ft, waves, ring = {5: (1, 8, 3), 6: (2, 8, 3), 7: (1, 16, 2)}[variant]
@@ -288,30 +275,28 @@ def launch(variant, M, N, K, gated=False, packed=False, splits=1):
                 "grid": n_out // 16 if gated else n_out // (16 * ft), "waves": waves,
                 "ring": ring, "slices": thin_slices(K // BK, waves)}
     nk = K // (BK * splits)
-    if variant == 1:
+    if family == "ws":
         return {"name": f"ws<{ws_mw(M)},{gated}>", "nk": nk, "splits": splits,
-                "grid": gemm_tiles(1, M, N, gated) * splits}
-    mt, mb = ws2_rows(M, variant_max_tiles(variant), packed)
-    if ws2_gated7(variant, M, N, gated, packed):
+                "grid": gemm_tiles(1, M, N) * splits}
+    mt, mb = ws2_rows(M, max_tiles, packed)
+    if gated and packed and bn == 256 and M <= 80 and N % 224 == 0:     # gemm_form: 7 waves
         mt = mt if mt in (2, 4) else 5
         return {"name": f"ws2<{mt},2,1,7,1>", "nk": nk, "splits": 1, "grid": N // 224}
-    nt, waves = (1, 4 if gated else 8) if variant == 3 else (2, 8)
-    if gated and variant == 3:
-        nt = 2
-    cells = (N // variant_bn(variant, gated)) * splits
+    nt, waves = (2, 4) if variant == 3 and gated else (bn // 128, 8)
+    cells = (N // bn) * splits
     return {"name": f"ws2<{mt},{nt},{gated},{waves},{int(packed)}>", "nk": nk, "splits": splits,
             "grid": ws2_grid(cells, mb), "cells": cells, "mblocks": mb}
 
 
 def all_instantiations():
-    """Every template instantiation the switches of gemm.hip can reach (104)."""
+    """Every template instantiation gemm_compiled admits, so gemm_launch can reach (104)."""
     out = [f"ws<{mw},{g}>" for g in (0, 1) for mw in range(1, WS_MAX_MW + 1)]
-    # dispatch_ws2<NT, GATED, WAVES, PACKED>: gated variant 3, gated, variant 3, the default;
+    # ws2<.., NT, GATED, WAVES, PACKED>: gated variant 3, gated, variant 3, the default;
     # the 5-tile row block on packed weights only (ws2_rows)
     for nt, g, waves in ((2, 1, 4), (2, 1, 8), (1, 0, 8), (2, 0, 8)):
         for p in (0, 1):
             out += [f"ws2<{mt},{nt},{g},{waves},{p}>" for mt in WS2_MT if mt != 5 or p]
-    out += [f"ws2<{mt},2,1,7,1>" for mt in (2, 4, 5)]                  # ws2_gated7
+    out += [f"ws2<{mt},2,1,7,1>" for mt in (2, 4, 5)]                  # the 7-wave form
     out += [f"thin<{mt},2,1,16,2>" for mt in (1, 2, 3)]                # gated variant 7
     for ft, g, waves, ring in ((2, 1, 8, 3), (1, 0, 8, 3), (2, 0, 8, 3), (1, 0, 16, 2)):
         out += [f"thin<{mt},{ft},{g},{waves},{ring}>" for mt in range(1, 6)]

@@ -13,8 +13,8 @@ of row M - 2) can only touch one row, so it must change >= 50 % of THAT row.
 Coverage: the restated dispatch, applied to the case list, reaches every template
 instantiation gemm.hip can launch, the ws / ws2 ones at nk 1, 2, 3, 4, 5 and 7, the thin
 ones at per-wave slice lengths 0, 1, RING - 1, RING, RING + 1 and >= 2 RING.  The
-restatement is pinned against the library's own cs_gemm_splits (a pure host function that
-depends on ws_mw / ws2_rows through gemm_tiles)."""
+restatement is pinned against the library's own cs_gemm_splits (a pure host function: the
+split of gemm_plan, which depends on kGemmVariants, resolve_variant, ws_mw and ws2_rows)."""
 import importlib
 import re
 
@@ -149,22 +149,26 @@ def test_guard_cases_cover_every_instantiation_with_a_ragged_tile():
         assert R.instantiation_of(c) == name and c.M % 16 != 0, (name, c)
 
 
-@pytest.mark.parametrize("N", [128, 256])
+@pytest.mark.parametrize("N", [128, 256, 384, 1792])
 def test_restated_dispatch_matches_cs_gemm_splits(pkg, N):
-    """cs_gemm_splits = f(gemm_tiles) = f(ws_mw, ws2_rows, variant_bn, resolve_variant): with K
-    so large that only the tile count bounds the split, every row count's tile count shows."""
+    """cs_gemm_splits = f(gemm_plan) = f(kGemmVariants, resolve_variant, ws_mw, ws2_rows): with K
+    so large that only the tile count bounds the split, every row count's tile count shows.
+    N = 384 takes the N % 256 fallback; 1792 = 8 x 224 is the 7-wave form's N."""
     L = importlib.import_module(pkg.__name__ + "._lib").load()
     K = 1 << 20
     rows = {}
-    for variant in (0, 1, 2, 3, 4):
+    for variant in range(8):
         for M in range(1, 601):
             want = int(L.cs_gemm_splits(M, N, K, 0, variant))
             assert R.gemm_splits(M, N, K, 0, variant) == want, (variant, M)
             rows.setdefault(variant, []).append(want)
     # it discriminates: the split drops where a variant takes a second or third row block
-    # (289 rows; variant 4: 145 and 433), and at N = 256 the 128- and 256-column variants differ
-    assert all(len(set(v)) >= 2 for v in rows.values())
-    assert len({tuple(v) for v in rows.values()}) >= (3 if N == 256 else 1)
+    # (289 rows; variant 4: 145 and 433), and where N % 256 == 0 the 128- and 256-column
+    # variants differ; the thin variants never split
+    assert all(len(set(rows[v])) >= 2 for v in range(5)) and all(set(rows[v]) == {1} for v in (5, 6, 7))
+    assert len({tuple(rows[v]) for v in range(5)}) >= (3 if N % 256 == 0 else 1)
+    if N % 256:
+        assert rows[0] == rows[2] == rows[4] == rows[3]
     for K in (64, 512, 1024, 1280, 1344, 2048, 14336):
         for variant in (0, 1, 3, 5, 7):
             for gated in (0, 1):
@@ -172,6 +176,7 @@ def test_restated_dispatch_matches_cs_gemm_splits(pkg, N):
                     assert R.gemm_splits(M, N, K, gated, variant) == \
                         int(L.cs_gemm_splits(M, N, K, gated, variant)), (M, K, gated, variant)
     assert R.gemm_splits(4, 100, 64, 0, 0) == int(L.cs_gemm_splits(4, 100, 64, 0, 0)) == 0
+    assert R.gemm_splits(4, N, 1 << 20, 0, 8) == int(L.cs_gemm_splits(4, N, 1 << 20, 0, 8)) == 1
 
 
 def test_restated_row_blocks():

@@ -66,17 +66,23 @@ def test_gemm_strided_operands_and_out(ops, dev):
 
 
 @pytest.mark.parametrize("col0", [0, 4])
-def test_gemm_split_k_into_strided_out(ops, dev, col0):
+@pytest.mark.parametrize("packed,M,K,splits", [(False, 24, 512, 4), (True, 17, 256, 2)],
+                         ids=["rowmajor", "packed"])
+def test_gemm_split_k_into_strided_out(ops, dev, packed, M, K, splits, col0):
     """A K split folds its partials with 16-byte stores: an out whose rows are only 8-byte
-    aligned (ld % 8 == 4, or a 4-column offset) must still get the split's exact result."""
-    M, N, K = 24, 256, 512
+    aligned (ld % 8 == 4, or a 4-column offset) must still get the split's exact result, on a
+    row-major and on a packed weight (one fallback serves both)."""
+    N = 256
     g = torch.Generator(device="cpu").manual_seed(5)
     x = torch.randn(M, K, generator=g).to(dev, torch.bfloat16)
     w = (torch.randn(N, K, generator=g) * 0.1).to(dev, torch.bfloat16)
-    want = ops.gemm(x, w, splits=4, variant=2)
+    want = ops.gemm(x, w, splits=splits, variant=2)
     ob = torch.zeros(M, N + 132, device=dev, dtype=torch.bfloat16)     # ld % 8 == 4
     view = ob[:, col0:col0 + N]
-    ops.gemm(x, w, splits=4, variant=2, out=view)
+    if packed:
+        ops.gemm_packed(x, ops.gemm_pack(w), splits=splits, variant=2, out=view)
+    else:
+        ops.gemm(x, w, splits=splits, variant=2, out=view)
     assert torch.equal(view, want)
     assert torch.all(ob[:, :col0] == 0) and torch.all(ob[:, col0 + N:] == 0)
 
