@@ -34,7 +34,8 @@ EXPORTED = (
     "cs_beam_decode_step", "cs_beam_select", "cs_prefix_attention_plan",
     "cs_prefix_attention", "cs_rope_place", "cs_add_rms_norm", "cs_gated_act",
     "cs_gemm_bf16", "cs_gemm_splits",
-    "cs_gemm_bf16_packed", "cs_gemm_pack", "cs_rope_place_splitk",
+    "cs_gemm_bf16_packed", "cs_gemm_pack", "cs_gemm_w8_pack", "cs_gemm_w8_pack_codes",
+    "cs_gemm_bf16_w8", "cs_gemm_bf16_w8_add", "cs_gemm_w8_splits", "cs_gemm_w8_max_rows", "cs_rope_place_splitk",
     "cs_add_rms_norm_splitk", "cs_prefix_attention_rows", "cs_rope_place_rows",
     "cs_rope_place_splitk_rows", "cs_hist_rows_update", "cs_nash_lottery", "cs_lottery_policy",
     "cs_maximin_lottery", "cs_policy_rollout", "cs_schulze",
@@ -148,6 +149,19 @@ def load():
     L.cs_gemm_bf16_packed.restype = ctypes.c_int
     L.cs_gemm_pack.argtypes = [vp, i64, i64, i64, vp, vp]
     L.cs_gemm_pack.restype = ctypes.c_int
+    L.cs_gemm_w8_pack.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp]
+    L.cs_gemm_w8_pack.restype = ctypes.c_int
+    L.cs_gemm_w8_pack_codes.argtypes = [vp, i64, i64, vp, vp]
+    L.cs_gemm_w8_pack_codes.restype = ctypes.c_int
+    L.cs_gemm_bf16_w8.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, i64, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, vp, vp]
+    L.cs_gemm_bf16_w8.restype = ctypes.c_int
+    L.cs_gemm_bf16_w8_add.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, i64, ctypes.c_int, vp, vp]
+    L.cs_gemm_bf16_w8_add.restype = ctypes.c_int
+    L.cs_gemm_w8_splits.argtypes = [i64, i64, i64, ctypes.c_int]
+    L.cs_gemm_w8_splits.restype = i64
+    L.cs_gemm_w8_max_rows.argtypes = []
+    L.cs_gemm_w8_max_rows.restype = i64
     i32 = ctypes.c_int32
     L.cs_rope_place_splitk.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp,
                                        vp, vp, i64, vp]

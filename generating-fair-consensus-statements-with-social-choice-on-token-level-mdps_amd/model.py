@@ -128,6 +128,8 @@ class Model:
         # cs_gemm_pack'ed copies of the decode-step weights the dispatch table runs packed
         # (pack_decode_weights; None until the first stream forward)
         self.wp: Optional[Dict[str, object]] = None
+        # FP8 copies of the decode-step weights (quantize_fp8; empty on a bf16 model)
+        self.w8: Dict[str, object] = {}
 
     def _fuse(self) -> None:
         """Per layer one [q; k; v] and one [gate; up] weight, so each is ONE GEMM; the
@@ -392,7 +394,9 @@ class Model:
         W = self.w["embed"] if self.cfg.tie_embeddings else self.w["lm_head"]
         if h.is_cuda and h.dim() == 2 and h.dtype == W.dtype == torch.bfloat16:
             from . import ops   # local: model.py stays importable without the library
-            pw = (self.wp or {}).get("lm_head")
+            pw = self.w8.get("lm_head") or (self.wp or {}).get("lm_head")
+            if "lm_head" in self.w8 and ops.gemm_w8_serves(h.shape[0], W.shape[0], W.shape[1]):
+                return ops.linear(h, W, out=out, packed=pw)
             if ops.gemm_choice(h.shape[0], W.shape[0], W.shape[1], packed=pw is not None) is not None:
                 return ops.linear(h, W, out=out, packed=pw)
         if out is not None:
@@ -410,6 +414,40 @@ class Model:
             out[p + "gate_up"] = (self.wf[p + "gate_up"], True)
             out[p + "w_down"] = (self.w[p + "w_down"], False)
         return out
+
+    @torch.no_grad()
+    def quantize_fp8(self) -> int:
+        """Round every decode weight (decode_weights: the fused q|k|v and gate|up, wo, w_down
+        and the head / tied embedding; the norms stay) onto the FP8 grid of ops.gemm_w8_pack,
+        in place, and keep the 1-byte copies in ``w8`` for the decode-step GEMMs
+        (cs_gemm_bf16_w8).  The bf16 weights become the twins value(code) * 2^e[n], so
+        prefill, the scoring forward and every bf16 GEMM compute on exactly the values the FP8
+        kernel reads; a weight with N % 128 or K % 64 non-zero is rounded all the same and
+        keeps no FP8 copy.  A second call changes nothing (a twin quantises to itself).  The
+        bf16 packs are dropped and rebuilt from the twins by the next stream forward.
+        Memory: the codes add half of the bf16 weights' bytes.  Returns the bytes of codes kept."""
+        from . import ops
+        if self.device.type != "cuda" or self.dtype != torch.bfloat16:
+            raise ops.CSError("quantize_fp8 needs a bf16 model on a HIP device")
+        w8, used = {}, 0
+        for name, (w, _) in self.decode_weights().items():
+            N, K = w.shape
+            if N % 16 == 0 and K % 64 == 0:
+                fw = ops.gemm_w8_pack(w, twin_out=w)
+            else:
+                # no layout for this shape: the same rounding through a padded copy
+                pad = torch.zeros(-(-N // 16) * 16, -(-K // 64) * 64, dtype=w.dtype, device=w.device)
+                pad[:N, :K] = w
+                ops.gemm_w8_pack(pad, twin_out=pad)
+                w.copy_(pad[:N, :K])
+                fw = None
+            if fw is not None and N % 128 == 0:
+                w8[name] = fw
+                used += N * K + N
+        torch.cuda.current_stream(self.device).synchronize()
+        self.w8 = w8
+        self.wp = None
+        return used
 
     @torch.no_grad()
     def pack_decode_weights(self, reserve_bytes: Optional[int] = None) -> int:
@@ -459,6 +497,8 @@ class Model:
         # forward or capture on another stream never reads a copy the GPU is still writing
         if wp:
             torch.cuda.current_stream(self.device).synchronize()
+        for name, fw in self.w8.items():      # the calls an FP8 copy leaves on the bf16 routes
+            fw.fallback = wp.get(name)
         self.wp = wp          # published whole: a concurrent forward sees all or nothing
         return used
 
@@ -513,6 +553,8 @@ class Model:
                 if self.wp is None:
                     self.pack_decode_weights()
         wp = self.wp or {}
+        if self.w8:           # an FP8 copy goes first; ops.linear falls back to the twin's routes
+            wp = {**wp, **self.w8}
         h = self._embed(tokens).contiguous()                 # the residual stream [n_tok, d]
         # every residual add + RMSNorm is one cs_add_rms_norm launch; h is updated in place
         x = ops.add_rms_norm(h, self.w["l0.attn_norm"], eps, plus_one=g2)

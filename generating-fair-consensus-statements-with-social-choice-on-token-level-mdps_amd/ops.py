@@ -1029,7 +1029,17 @@ def linear(x: torch.Tensor, w: torch.Tensor, *, gated: bool = False, act: str = 
     dispatch table measured faster for this shape: cs_gemm_bf16 (on the packed copy
     ``packed`` of w when given and fastest) or hipBLASLt (+ cs_gated_act).
     fold=False: a K-split cs_gemm_bf16 returns its unfolded SplitPartials (for an
-    add_rms_norm to fold); every other path returns the bf16 tensor as usual."""
+    add_rms_norm to fold); every other path returns the bf16 tensor as usual.
+    packed an Fp8Weight (w is then its bf16 twin): a row count and shape cs_gemm_bf16_w8 serves
+    (gemm_w8_serves) runs on the 1-byte codes; every other call continues below on the twin."""
+    if isinstance(packed, Fp8Weight):
+        fw, packed = packed, packed.fallback
+        if x.dim() == 2 and gemm_w8_serves(x.shape[0], fw.N, fw.K, gated) and _w8_operands(x, fw):
+            if not fold and not gated and out is None:
+                splits = int(_lib.load().cs_gemm_w8_splits(x.shape[0], fw.N, fw.K, 0))
+                if splits > 1:
+                    return gemm_w8_partials(x, fw, splits=splits)
+            return gemm_w8(x, fw, gated=gated, act=act, out=out)
     if x.is_cuda and x.dim() == 2:
         ch = gemm_choice(x.shape[0], w.shape[0], w.shape[1], gated, packed=packed is not None)
         if ch is not None:
@@ -1060,7 +1070,20 @@ def linear_into_residual(x: torch.Tensor, w: torch.Tensor, h: torch.Tensor, *,
     fp32 and rounded once) when the dispatch table leaves this shape on hipBLASLt; returns
     False (nothing done) otherwise, and the caller takes ``linear`` + the residual add.
     For the many-row scoring forward: the residual add's launch then only normalises (one
-    read and one write of the rows instead of two and two)."""
+    read and one write of the rows instead of two and two).  packed an Fp8Weight: a shape
+    cs_gemm_bf16_w8 serves adds its product in that kernel's own epilogue (gemm_w8_add: fp32
+    sum + h, rounded once -- the rounding of the epilogue the bf16 twin takes here, so the FP8
+    engine differs from the twin's by accumulation order alone); otherwise as without it, on
+    the twin w."""
+    if isinstance(packed, Fp8Weight):
+        fw, packed = packed, packed.fallback
+        if (x.dim() == 2 and h.dim() == 2 and h.is_contiguous() and h.dtype == torch.bfloat16
+                and h.shape == (x.shape[0], fw.N) and h.is_cuda
+                and gemm_w8_serves(x.shape[0], fw.N, fw.K, False) and _w8_operands(x, fw)):
+            if gemm_choice(x.shape[0], fw.N, fw.K, False, packed=packed is not None) is not None:
+                return False      # the twin folds this shape in the residual add: so does the FP8 route
+            gemm_w8_add(x, fw, h)
+            return True
     if not (x.is_cuda and x.dim() == 2 and h.dim() == 2 and h.is_contiguous() and
             h.dtype == x.dtype == w.dtype == torch.bfloat16 and h.shape == (x.shape[0], w.shape[0])):
         return False
@@ -1188,6 +1211,171 @@ def gemm_packed_partials(x: torch.Tensor, pw: PackedWeight, *, splits: int,
 def gemm_partials(x: torch.Tensor, w: torch.Tensor, *, splits: int, variant: int = 0) -> SplitPartials:
     """The fp32 partials [splits, M, N] of cs_gemm_bf16 with a K split, unfolded (y = NULL)."""
     return _gemm("gemm_partials", x, w, splits=splits, variant=variant, partials=True)
+
+
+class Fp8Weight:
+    """A [N, K] weight as OCP e4m3fn codes with one power-of-two scale per row, in
+    cs_gemm_w8_pack's fragment-major layout: ``data`` the packed codes (uint8 [N * K]), ``exps``
+    the row exponents (int8 [N]).  ``fallback``: the cs_gemm_pack'ed copy of its bf16 twin, if
+    one is kept, for the calls that stay on the bf16 routes."""
+
+    def __init__(self, data: torch.Tensor, exps: torch.Tensor, N: int, K: int,
+                 fallback: Optional[PackedWeight] = None):
+        self.data, self.exps, self.N, self.K, self.fallback = data, exps, int(N), int(K), fallback
+
+    @property
+    def shape(self):
+        return (self.N, self.K)
+
+
+GEMM_W8_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned",
+                             "gemm_w8_mi355x.json")
+_w8_excluded: Optional[frozenset] = None
+_w8_max_rows: Optional[int] = None
+
+
+def gemm_w8_max_rows() -> int:
+    """The largest row count cs_gemm_bf16_w8 takes (cs_gemm_w8_max_rows)."""
+    global _w8_max_rows
+    if _w8_max_rows is None:
+        _w8_max_rows = int(_lib.load().cs_gemm_w8_max_rows())
+    return _w8_max_rows
+
+
+def gemm_w8_serves(M: int, N: int, K: int, gated: bool = False) -> bool:
+    """Whether ``linear`` runs an Fp8Weight of this shape on cs_gemm_bf16_w8 at M rows: M within
+    the kernel's range, N % 128 == 0, K % 64 == 0, and "M,N,K,gated" not in the exclusion list
+    tuned/gemm_w8_mi355x.json (tools/w8_bench.py: the shapes measured no faster than the bf16
+    route of the twin; read only)."""
+    global _w8_excluded
+    if _w8_excluded is None:
+        ex = []
+        if os.path.exists(GEMM_W8_TABLE):
+            with open(GEMM_W8_TABLE) as f:
+                ex = json.load(f).get("exclude", [])
+        _w8_excluded = frozenset(ex)
+    if M < 1 or M > gemm_w8_max_rows() or N % 128 or K % 64:
+        return False
+    return f"{M},{N},{K},{int(bool(gated))}" not in _w8_excluded
+
+
+def _w8_operands(x: torch.Tensor, fw: Fp8Weight) -> bool:
+    """Whether cs_gemm_bf16_w8 takes x: bf16 [M, K] on the GPU, unit column stride, 16-byte
+    aligned rows."""
+    return (x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] == fw.K
+            and x.stride(1) == 1 and (x.stride(0) % 8 == 0 or x.shape[0] <= 1)
+            and x.data_ptr() % 16 == 0)
+
+
+def gemm_w8_pack(w: torch.Tensor, twin_out: Optional[torch.Tensor] = None) -> Fp8Weight:
+    """The FP8 copy of w [N, K] bf16 (cs_gemm_w8_pack; N % 16 == 0, K % 64 == 0): codes =
+    e4m3_rne(w * 2^-e[n]) with e[n] the smallest exponent that brings the row's amax to <= 448.
+    twin_out (bf16 [N, K]; may be w itself) receives the twin value(code) * 2^e[n], the bf16
+    weight every other route then computes on.  A non-finite input or a row whose twin is no
+    bf16 number raises CSError and leaves twin_out untouched (reads the status: a host sync)."""
+    L = _lib.load()
+    if w.dim() != 2 or w.dtype != torch.bfloat16 or w.stride(1) != 1:
+        raise CSError("gemm_w8_pack needs a bf16 [N, K] tensor with unit column stride")
+    N, K = w.shape
+    if twin_out is not None and (twin_out.shape != w.shape or twin_out.dtype != torch.bfloat16
+                                 or twin_out.stride(1) != 1):
+        raise CSError("twin_out must be a bf16 [N, K] tensor with unit column stride")
+    _require_cuda(w, twin_out)
+    data = torch.empty(N * K, dtype=torch.uint8, device=w.device)
+    exps = torch.empty(N, dtype=torch.int8, device=w.device)
+    status = torch.empty(1, dtype=torch.int32, device=w.device)
+    rc = L.cs_gemm_w8_pack(w.data_ptr(), w.stride(0), N, K, data.data_ptr(), exps.data_ptr(),
+                           _ptr(twin_out), 0 if twin_out is None else twin_out.stride(0),
+                           status.data_ptr(), _stream())
+    _lib.check(rc, "cs_gemm_w8_pack")
+    st = int(status.item())
+    if st:
+        why = " and ".join(t for b, t in ((1, "an Inf or NaN input"),
+                                          (2, "a row whose FP8 twin is no bf16 number")) if st & b)
+        raise CSError(f"gemm_w8_pack refused the weight (status {st}): {why}")
+    return Fp8Weight(data, exps, N, K)
+
+
+def gemm_w8_from_codes(codes: torch.Tensor, exps: torch.Tensor) -> Fp8Weight:
+    """An Fp8Weight of given e4m3fn codes (uint8 [N, K]) and row exponents (int8 [N]):
+    cs_gemm_w8_pack_codes, the layout permutation alone."""
+    L = _lib.load()
+    if codes.dim() != 2 or codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise CSError("gemm_w8_from_codes needs contiguous uint8 codes [N, K]")
+    N, K = codes.shape
+    if exps.shape != (N,) or exps.dtype != torch.int8:
+        raise CSError("exps must be int8 [N]")
+    _require_cuda(codes, exps)
+    data = torch.empty(N * K, dtype=torch.uint8, device=codes.device)
+    rc = L.cs_gemm_w8_pack_codes(codes.data_ptr(), N, K, data.data_ptr(), _stream())
+    _lib.check(rc, "cs_gemm_w8_pack_codes")
+    return Fp8Weight(data, exps.contiguous().clone(), N, K)
+
+
+def _gemm_w8(x: torch.Tensor, fw: Fp8Weight, gated: bool = False, act: str = "silu",
+             splits: int = 0, out: Optional[torch.Tensor] = None, partials: bool = False):
+    L = _lib.load()
+    if not _w8_operands(x, fw):
+        raise CSError("gemm_w8 needs bf16 x [M, K] with unit column stride and 16-byte aligned rows")
+    if partials and splits < 2:
+        raise CSError("gemm_w8_partials needs splits >= 2")
+    M, N, K = x.shape[0], fw.N, fw.K
+    n_out = N // 2 if gated else N
+    if out is None and not partials:
+        out = torch.empty(M, n_out, dtype=torch.bfloat16, device=x.device)
+    if out is not None and (out.shape != (M, n_out) or out.dtype != torch.bfloat16 or out.stride(1) != 1):
+        raise CSError("out must be a bf16 [M, N] tensor with unit column stride")
+    _require_cuda(x, fw.data, fw.exps, out)
+    if gated:
+        splits = 1
+    elif splits <= 0:
+        splits = max(1, int(L.cs_gemm_w8_splits(M, N, K, 0)))
+    ldx = x.stride(0) if M > 1 else K
+    ldy = 0 if out is None else out.stride(0) if M > 1 else n_out
+    if out is not None and splits > 1 and (ldy % 8 or out.data_ptr() % 16):
+        # the split-K fold stores 16-byte vectors: fold into an aligned tensor, then copy
+        out.copy_(_gemm_w8(x, fw, splits=splits))
+        return out
+    part = torch.empty(splits, M, N, dtype=torch.float32, device=x.device) if splits > 1 else None
+    rc = L.cs_gemm_bf16_w8(x.data_ptr(), ldx, fw.data.data_ptr(), fw.exps.data_ptr(), _ptr(out), ldy,
+                           M, N, K, splits, int(bool(gated)), _ACT[act], _ptr(part), _stream())
+    _lib.check(rc, "cs_gemm_bf16_w8")
+    return SplitPartials(part) if partials else out
+
+
+def gemm_w8(x: torch.Tensor, fw: Fp8Weight, *, gated: bool = False, act: str = "silu",
+            splits: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = bf16(2^e[n] * sum_k x[m][k] * value(code[n][k])) (cs_gemm_bf16_w8): ops.gemm on an
+    Fp8Weight, M <= gemm_w8_max_rows().  It differs from ops.gemm on the weight's bf16 twin only
+    by the accumulation order.  gated, act, splits, out as ops.gemm."""
+    return _gemm_w8(x, fw, gated, act, splits, out)
+
+
+def gemm_w8_add(x: torch.Tensor, fw: Fp8Weight, h: torch.Tensor, *, splits: int = 0) -> torch.Tensor:
+    """h += x @ w.T in place (cs_gemm_bf16_w8_add): h [M, N] bf16; the fp32 product (a K split:
+    its fold) is added to h before the one rounding to bf16."""
+    L = _lib.load()
+    if not _w8_operands(x, fw):
+        raise CSError("gemm_w8_add needs bf16 x [M, K] with unit column stride and 16-byte aligned rows")
+    M, N, K = x.shape[0], fw.N, fw.K
+    if h.shape != (M, N) or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise CSError("h must be a bf16 [M, N] tensor with unit column stride")
+    _require_cuda(x, fw.data, fw.exps, h)
+    if splits <= 0:
+        splits = max(1, int(L.cs_gemm_w8_splits(M, N, K, 0)))
+    ldh = h.stride(0) if M > 1 else N
+    if splits > 1 and (ldh % 8 or h.data_ptr() % 16):
+        raise CSError("gemm_w8_add with a K split needs h 16-byte aligned with a row stride % 8 == 0")
+    part = torch.empty(splits, M, N, dtype=torch.float32, device=x.device) if splits > 1 else None
+    rc = L.cs_gemm_bf16_w8_add(x.data_ptr(), x.stride(0) if M > 1 else K, fw.data.data_ptr(),
+                               fw.exps.data_ptr(), _ptr(h), ldh, M, N, K, splits, _ptr(part), _stream())
+    _lib.check(rc, "cs_gemm_bf16_w8_add")
+    return h
+
+
+def gemm_w8_partials(x: torch.Tensor, fw: Fp8Weight, *, splits: int) -> SplitPartials:
+    """The fp32 partials [splits, M, N] of cs_gemm_bf16_w8 with a K split, unfolded (y = NULL)."""
+    return _gemm_w8(x, fw, splits=splits, partials=True)
 
 
 def hist_rows_update(src_rows: torch.Tensor, dst_rows: torch.Tensor, parent: torch.Tensor,

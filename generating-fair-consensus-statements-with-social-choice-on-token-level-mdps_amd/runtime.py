@@ -11,6 +11,11 @@ Here the identifier resolves to a local ``ScoringEngine`` on the current HIP dev
   * ``random:<preset>`` (e.g. ``random:llama-3.1-8b``): an architecture-exact,
     random-initialised bf16 model with a full-vocabulary synthetic tokenizer — for
     throughput benchmarks only, the statements it produces mean nothing.
+An identifier ending in ``@fp8`` resolves as the identifier without the suffix (a checkpoint
+directory or ``random:<preset>``), and the engine built for it is quantised once
+(``Model.quantize_fp8``: FP8 e4m3 copies of the projection weights for the decode-step GEMMs,
+the bf16 weights rounded onto the same grid) and cached under the full identifier; the
+identifier without the suffix keeps its own, unrounded engine.
 A real model id with none of these raises: random weights are never substituted
 silently (set CS_ALLOW_RANDOM_INIT=1 to get the random-init model with a warning).
 
@@ -267,6 +272,16 @@ def use_gemm_tuning(path: Optional[str] = None) -> Optional[str]:
         return path
 
 
+FP8_SUFFIX = "@fp8"
+
+
+def split_fp8_id(model_identifier: str) -> Tuple[str, bool]:
+    """(the identifier without a trailing ``@fp8``, whether it had one)."""
+    if model_identifier.endswith(FP8_SUFFIX) and len(model_identifier) > len(FP8_SUFFIX):
+        return model_identifier[:-len(FP8_SUFFIX)], True
+    return model_identifier, False
+
+
 def get_engine(model_identifier: str) -> Tuple[ScoringEngine, CharTokenizer]:
     """The engine serving ``model_identifier``; loaded on first use.  A load (minutes for a
     70B checkpoint) holds only that identifier's loading lock, not the registry lock, so
@@ -281,8 +296,19 @@ def get_engine(model_identifier: str) -> Tuple[ScoringEngine, CharTokenizer]:
         with _lock:
             if model_identifier in _ENGINES:     # loaded by another thread meanwhile
                 return _ENGINES[model_identifier]
-            path = _model_dir(model_identifier)
-        ent = _load_engine(model_identifier, path)
+            base, fp8 = split_fp8_id(model_identifier)
+            path = _model_dir(base)
+            loadable = path is not None or base.startswith("random:") or \
+                os.environ.get("CS_ALLOW_RANDOM_INIT") == "1"
+            if fp8 and not loadable and base in _ENGINES:
+                raise ops.CSError(
+                    f"model {base!r} is a registered engine object: quantise a copy of it "
+                    f"(engine.model.quantize_fp8()) and register that as {model_identifier!r}")
+        # an @fp8 id builds its own engine: the one cached under the plain id stays unrounded
+        ent = _load_engine(base, path)
+        if fp8:
+            with device_lock(ent[0].model.device):
+                ent[0].model.quantize_fp8()      # (CSError unless bf16 on a HIP device)
         if os.environ.get("CS_GEMM_TUNING", "0") != "0":
             use_gemm_tuning()
         with _lock:

@@ -631,6 +631,66 @@ int cs_gemm_bf16_packed(const void* x, int64_t ldx, const void* w_packed, void* 
                         int variant, float* workspace, cs_stream_t stream);
 
 /*
+ * cs_gemm_w8_pack — W [N, K] bf16 (row stride ldw) quantised to OCP e4m3fn codes (bias 7,
+ * largest finite value 448, no infinities, NaN at 0x7f / 0xff; not the fnuz form) with one
+ * power-of-two scale per row:
+ *   row_exp[n] = the smallest integer e with amax_n * 2^-e <= 448 (an all-zero row: 0), int8
+ *   code[n][k] = e4m3_rne(w[n][k] * 2^-row_exp[n])   (subnormal codes kept, NaN never produced)
+ *   twin[n][k] = value(code[n][k]) * 2^row_exp[n]    (exactly a bf16 number)
+ * codes_packed (N * K bytes) is fragment-major: the 16-row tile T's 64-deep K step s is 1 KB at
+ * byte (T * K / 64 + s) * 1024, lane-linear (lane l's 16 bytes = row 16T + l % 16; byte 8h + j
+ * of them = k 64s + 32h + 8 (l / 16) + j, h = 0, 1, j = 0..7):
+ *   codes_packed[(T * K / 64 + s) * 1024 + 16 l + 8 h + j] = code[16T + l % 16][64s + 32h + 8 (l / 16) + j]
+ * twin (row stride ldt) may be NULL, or w itself (in place).  status (device int32) is set to 0,
+ * or to 1 (an input is Inf or NaN) | 2 (a row's exponent leaves int8, or one of its twin values
+ * is no bf16 number: it overflows or falls below bf16's subnormal grid); when it is not 0,
+ * codes_packed, row_exp and twin are left untouched.  N % 16 == 0, K % 64 == 0, ldw and ldt
+ * multiples of 8, 16-byte aligned.  No host sync.  Done once per weight, at model load.
+ *
+ * cs_gemm_w8_pack_codes — the same permutation of given codes [N, K] (row-major bytes).
+ *
+ * cs_gemm_bf16_w8 — cs_gemm_bf16_packed on such a weight:
+ *   Y[m][n] = bf16_rne(2^row_exp[n] * sum_k X[m][k] * value(code[n][k])),
+ * codes converted to bf16 in registers, v_mfma_f32_16x16x32_bf16 accumulation in fp32, the scale
+ * applied to the fp32 sum (to each K split's partial) before any rounding.  Same rules: N a
+ * multiple of 128, K of 64 * splits; splits > 1 (at most 16) folds fp32 partials
+ * [splits][M][N] (workspace) in split order, y = NULL leaves them unfolded for
+ * cs_rope_place_splitk / cs_add_rms_norm_splitk; splits <= 0 takes cs_gemm_w8_splits; gated = 1
+ * pairs gate row f with up row N / 2 + f (each with its own exponent) and writes act(gate) * up
+ * with cs_gated_act's roundings (no K split).  M <= cs_gemm_w8_max_rows() (80: the decode
+ * steps, where a projection is a weight stream); above it CS_ERR_INVALID, nothing launched.
+ * ldx a multiple of 8, ldy of 4; x and the codes 16-byte aligned, row_exp 4-byte.
+ * Deterministic (no atomics), no host sync.
+ *
+ * cs_gemm_bf16_w8_add — the residual form (not gated): h [M, N] (row stride ldh) is read and
+ * rewritten in place, h[m][n] = bf16_rne(h[m][n] + 2^row_exp[n] * sum_k ...): the fp32 product is
+ * added to the residual before the ONE rounding, as a BLAS epilogue with beta = 1 adds it (a
+ * K split adds in its fold).  Same shape, split, alignment and M rules as cs_gemm_bf16_w8 with
+ * y = h.
+ *
+ * Replaces: the same projections of the remote forward as cs_gemm_bf16
+ *   (src/utils.py:249-259), on a 1-byte weight stream.
+ */
+int cs_gemm_w8_pack(const void* w, int64_t ldw, int64_t N, int64_t K, void* codes_packed,
+                    int8_t* row_exp, void* twin, int64_t ldt, int32_t* status, cs_stream_t stream);
+
+int cs_gemm_w8_pack_codes(const void* codes, int64_t N, int64_t K, void* codes_packed,
+                          cs_stream_t stream);
+
+int cs_gemm_bf16_w8(const void* x, int64_t ldx, const void* codes_packed, const int8_t* row_exp,
+                    void* y, int64_t ldy, int64_t M, int64_t N, int64_t K, int splits, int gated,
+                    int act, float* workspace, cs_stream_t stream);
+
+int cs_gemm_bf16_w8_add(const void* x, int64_t ldx, const void* codes_packed, const int8_t* row_exp,
+                        void* h, int64_t ldh, int64_t M, int64_t N, int64_t K, int splits,
+                        float* workspace, cs_stream_t stream);
+
+/* cs_gemm_w8_splits — the K split cs_gemm_bf16_w8 takes for splits <= 0 (>= 1; 0 on a shape it
+ * rejects: M, N or K <= 0, N % 128 or K % 64 != 0).  cs_gemm_w8_max_rows — its largest M. */
+int64_t cs_gemm_w8_splits(int64_t M, int64_t N, int64_t K, int gated);
+int64_t cs_gemm_w8_max_rows(void);
+
+/*
  * cs_nash_lottery — the lottery over m complete statements that maximises Nash welfare
  * F(p) = sum_i log(U_i . p), for P independent problems in one launch, one workgroup each:
  * Frank-Wolfe towards the vertex e_j* of largest gradient g_j = sum_i U[i,j] / a_i (a = U p,
