@@ -1702,18 +1702,30 @@ int cs_hist_rows_update(const int32_t* src_rows, int32_t* dst_rows, const int64_
 }  // extern "C"
 
 namespace {
-int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t splits,
-                    const float* inv_freq, const int32_t* prefix_len, const int32_t* group_prefix,
-                    int32_t n_groups, const int32_t* hist_base, int32_t n_str, int32_t T, int32_t H,
-                    int32_t Hkv, int32_t D, void* q_out, void* k_hist, void* vt_hist,
-                    int64_t ld_hist, int32_t v_rows, cs_stream_t stream) {
-  if (n_groups < 0 || n_str < 0 || T < 0) return fail(CS_ERR_INVALID, "cs_rope_place: negative size");
+// `name`: the entry point that was called, for the messages
+int rope_place_impl(const char* name, const void* qkv, int64_t ld_qkv, const float* part,
+                    int32_t splits, const float* inv_freq, const int32_t* prefix_len,
+                    const int32_t* group_prefix, int32_t n_groups, const int32_t* hist_base,
+                    int32_t n_str, int32_t T, int32_t H, int32_t Hkv, int32_t D, void* q_out,
+                    void* k_hist, void* vt_hist, int64_t ld_hist, int32_t v_rows, cs_stream_t stream) {
+  const std::string nm(name);
+  if (n_groups < 0 || n_str < 0 || T < 0) return fail(CS_ERR_INVALID, nm + ": negative size");
   if (n_groups == 0 || n_str == 0 || T == 0) return CS_OK;
   if (H <= 0 || Hkv <= 0 || D <= 0 || D % 2 != 0 || ld_qkv < static_cast<int64_t>(H + 2 * Hkv) * D)
-    return fail(CS_ERR_INVALID, "cs_rope_place: bad head layout");
-  if (ld_hist < T) return fail(CS_ERR_INVALID, "cs_rope_place: ld_hist < T");
+    return fail(CS_ERR_INVALID, nm + ": bad head layout");
+  if (ld_hist < T) return fail(CS_ERR_INVALID, nm + ": ld_hist < T");
   if (!inv_freq || !prefix_len || !hist_base || !q_out || !k_hist || !vt_hist)
-    return fail(CS_ERR_INVALID, "cs_rope_place: NULL pointer");
+    return fail(CS_ERR_INVALID, nm + ": NULL pointer");
+  // the blocked V layout is whole 32-slot tiles per head: another ld_hist would put a head's
+  // last slots into the next head's first tile
+  if (!v_rows && ld_hist % 32 != 0)
+    return fail(CS_ERR_INVALID, nm + ": ld_hist must be a multiple of 32 (V^T tiles)");
+  // 16-byte stores to the outputs; the 4-pair items' 8-byte loads of the projection
+  if (reinterpret_cast<uintptr_t>(q_out) % 16 || reinterpret_cast<uintptr_t>(k_hist) % 16 ||
+      reinterpret_cast<uintptr_t>(vt_hist) % 16)
+    return fail(CS_ERR_INVALID, nm + ": q_out, k_hist and vt_hist must be 16-byte aligned");
+  if (!part && (reinterpret_cast<uintptr_t>(qkv) % 8 || ld_qkv % 4 != 0))
+    return fail(CS_ERR_INVALID, nm + ": qkv must be 8-byte aligned, ld_qkv a multiple of 4");
   RopeParams r;
   r.qkv = static_cast<const __bf16*>(qkv);
   r.ldqkv = ld_qkv;
@@ -1734,19 +1746,19 @@ int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t 
   r.H = H;
   r.Hkv = Hkv;
   r.D = D;
-  if (D % 8 != 0 || D > 256) return fail(CS_ERR_INVALID, "cs_rope_place: head_dim must be a multiple of 8, <= 256");
-  if (r.n_tok > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_rope_place: too many tokens");
+  if (D % 8 != 0 || D > 256) return fail(CS_ERR_INVALID, nm + ": head_dim must be a multiple of 8, <= 256");
+  if (r.n_tok > 0x7fffffffLL) return fail(CS_ERR_INVALID, nm + ": too many tokens");
   // V by 32-slot tiles when the streams carry many tokens
   const int64_t n_tiles = ld_hist / 32;
   const int64_t n_vwg = static_cast<int64_t>(n_groups) * n_str * Hkv * n_tiles;
-  r.skip_v = (!part && !v_rows && T >= 32 && ld_hist % 32 == 0 && ld_qkv % 8 == 0 &&
+  r.skip_v = (!part && !v_rows && T >= 32 && ld_qkv % 8 == 0 &&
               reinterpret_cast<uintptr_t>(qkv) % 16 == 0 && n_vwg <= 0x7fffffffLL) ? 1 : 0;
   // 8-pair (16-byte) items when every head's halves are 16-byte aligned, else 4-pair
   const bool p8 = part ? true
                        : (ld_qkv % 8 == 0 && reinterpret_cast<uintptr_t>(qkv) % 16 == 0 && D % 16 == 0);
   const int64_t n_items = static_cast<int64_t>(H + 2 * Hkv) * (D / 2) / (p8 ? 8 : 4);
   const int64_t n_split = (n_items + kRopeItems - 1) / kRopeItems;
-  if (r.n_tok * n_split > 0x7fffffffLL) return fail(CS_ERR_INVALID, "cs_rope_place: too many tokens");
+  if (r.n_tok * n_split > 0x7fffffffLL) return fail(CS_ERR_INVALID, nm + ": too many tokens");
   const dim3 grid(static_cast<uint32_t>(r.n_tok * n_split));
   if (part && splits <= 2)
     hipLaunchKernelGGL((rope_place_kernel<8, true, 2>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -1766,7 +1778,7 @@ int rope_place_impl(const void* qkv, int64_t ld_qkv, const float* part, int32_t 
   if (r.skip_v)
     hipLaunchKernelGGL(v_tile_place_kernel, dim3(static_cast<uint32_t>(n_vwg)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), r, static_cast<int32_t>(n_tiles));
-  return check_launch("cs_rope_place");
+  return check_launch(name);
 }
 
 // the checks the two split-K entry points share (`name`: the entry point's, for the messages)
@@ -1780,7 +1792,7 @@ int rope_place_splitk_impl(const char* name, const float* part, int32_t splits, 
   if (T >= 32) return fail(CS_ERR_INVALID, nm + ": T < 32 only (fold first for chunks)");
   if (reinterpret_cast<uintptr_t>(part) % 16 || D % 16)
     return fail(CS_ERR_INVALID, nm + ": partials 16-byte aligned, head_dim % 16 == 0");
-  return rope_place_impl(nullptr, static_cast<int64_t>(H + 2 * Hkv) * D, part, splits, inv_freq,
+  return rope_place_impl(name, nullptr, static_cast<int64_t>(H + 2 * Hkv) * D, part, splits, inv_freq,
                          prefix_len, group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out,
                          k_hist, vt_hist, ld_hist, v_rows, stream);
 }
@@ -1793,8 +1805,9 @@ int cs_rope_place(const void* qkv, int64_t ld_qkv, const float* inv_freq, const 
                   int32_t n_str, int32_t T, int32_t H, int32_t Hkv, int32_t D, void* q_out,
                   void* k_hist, void* vt_hist, int64_t ld_hist, cs_stream_t stream) {
   if (!qkv) return fail(CS_ERR_INVALID, "cs_rope_place: NULL pointer");
-  return rope_place_impl(qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix, n_groups,
-                         hist_base, n_str, T, H, Hkv, D, q_out, k_hist, vt_hist, ld_hist, 0, stream);
+  return rope_place_impl("cs_rope_place", qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix,
+                         n_groups, hist_base, n_str, T, H, Hkv, D, q_out, k_hist, vt_hist, ld_hist, 0,
+                         stream);
 }
 
 int cs_rope_place_rows(const void* qkv, int64_t ld_qkv, const float* inv_freq,
@@ -1803,8 +1816,9 @@ int cs_rope_place_rows(const void* qkv, int64_t ld_qkv, const float* inv_freq,
                        int32_t D, void* q_out, void* k_hist, void* v_hist, int64_t ld_hist,
                        cs_stream_t stream) {
   if (!qkv) return fail(CS_ERR_INVALID, "cs_rope_place_rows: NULL pointer");
-  return rope_place_impl(qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len, group_prefix, n_groups,
-                         hist_base, n_str, T, H, Hkv, D, q_out, k_hist, v_hist, ld_hist, 1, stream);
+  return rope_place_impl("cs_rope_place_rows", qkv, ld_qkv, nullptr, 1, inv_freq, prefix_len,
+                         group_prefix, n_groups, hist_base, n_str, T, H, Hkv, D, q_out, k_hist, v_hist,
+                         ld_hist, 1, stream);
 }
 
 int cs_rope_place_splitk(const float* part, int32_t splits, const float* inv_freq,

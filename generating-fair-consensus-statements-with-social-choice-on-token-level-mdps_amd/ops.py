@@ -826,33 +826,27 @@ def rope_place(qkv: "torch.Tensor | SplitPartials", inv_freq: torch.Tensor, pref
     V [S, Hkv, ldh, D] (cs_rope_place_rows, the cs_prefix_attention_rows history)."""
     L = _lib.load()
     vshape = (lambda S, ldh: (S, Hkv, ldh, D)) if v_rows else (lambda S, ldh: (S, Hkv, ldh // 32, D, 32))
-    sfx = "_rows" if v_rows else ""
-    if isinstance(qkv, SplitPartials):
-        part = qkv.part
-        S, Hkv2, ldh, Dk = k_hist.shape
-        n_tok = part.shape[1]
-        if (part.dim() != 3 or part.dtype != torch.float32 or not part.is_contiguous()
-                or part.shape[2] != (H + 2 * Hkv) * D):
+    split = isinstance(qkv, SplitPartials)
+    name = "cs_rope_place" + ("_splitk" if split else "") + ("_rows" if v_rows else "")
+    if split:
+        src = qkv.part
+        if (src.dim() != 3 or src.dtype != torch.float32 or not src.is_contiguous()
+                or src.shape[2] != (H + 2 * Hkv) * D):
             raise CSError("qkv partials must be contiguous float32 [splits, n_tok, (H + 2 Hkv) D]")
-        if Hkv2 != Hkv or Dk != D or tuple(vt_hist.shape) != vshape(S, ldh):
-            raise CSError("k_hist [S, Hkv, ldh, D] / vt_hist [S, Hkv, ldh/32, D, 32] layout mismatch")
-        if n_tok != S * T or S % n_str != 0:
-            raise CSError("qkv rows must be streams x T")
-        if tuple(q_out.shape) != (n_tok, H, D) or q_out.dtype != torch.bfloat16 or not q_out.is_contiguous():
-            raise CSError("q_out must be a contiguous [n_tok, H, D] bfloat16 tensor")
-        _require_cuda(part, inv_freq, prefix_len, hist_base, q_out, k_hist, vt_hist, group_prefix)
-        rc = getattr(L, "cs_rope_place_splitk" + sfx)(part.data_ptr(), part.shape[0], inv_freq.data_ptr(),
-                                    prefix_len.data_ptr(),
-                                    group_prefix.data_ptr() if group_prefix is not None else None,
-                                    S // n_str, hist_base.data_ptr(), n_str, T, H, Hkv, D,
-                                    q_out.data_ptr(), k_hist.data_ptr(), vt_hist.data_ptr(), ldh,
-                                    _stream())
-        _lib.check(rc, "cs_rope_place_splitk" + sfx)
-        return q_out
-    if qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or qkv.stride(1) != 1:
-        raise CSError("qkv must be a 2-D bfloat16 tensor with unit column stride")
-    n_tok = qkv.shape[0]
+        n_tok = src.shape[1]
+        head = (src.data_ptr(), src.shape[0])
+    else:
+        src = qkv
+        if src.dim() != 2 or src.dtype != torch.bfloat16 or src.stride(1) != 1:
+            raise CSError("qkv must be a 2-D bfloat16 tensor with unit column stride")
+        n_tok = src.shape[0]
+        ld = src.stride(0) if n_tok > 1 else src.shape[1]
+        if src.data_ptr() % 8 or ld % 4 != 0:
+            raise CSError(f"{name}: qkv must be 8-byte aligned, ld_qkv a multiple of 4")
+        head = (src.data_ptr(), ld)
     S, Hkv2, ldh, Dk = k_hist.shape
+    if not v_rows and ldh % 32 != 0:
+        raise CSError(f"{name}: ld_hist must be a multiple of 32 (V^T tiles)")
     if Hkv2 != Hkv or Dk != D or tuple(vt_hist.shape) != vshape(S, ldh):
         raise CSError("k_hist [S, Hkv, ldh, D] / vt_hist [S, Hkv, ldh/32, D, 32] layout mismatch")
     if n_tok != S * T or S % n_str != 0:
@@ -861,13 +855,14 @@ def rope_place(qkv: "torch.Tensor | SplitPartials", inv_freq: torch.Tensor, pref
         raise CSError("q_out must be a contiguous [n_tok, H, D] bfloat16 tensor")
     if inv_freq.dtype != torch.float32 or inv_freq.numel() != D // 2:
         raise CSError("inv_freq must be float32 [D/2]")
-    _require_cuda(qkv, inv_freq, prefix_len, hist_base, q_out, k_hist, vt_hist, group_prefix)
-    ld = qkv.stride(0) if n_tok > 1 else qkv.shape[1]
-    rc = getattr(L, "cs_rope_place" + sfx)(qkv.data_ptr(), ld, inv_freq.data_ptr(), prefix_len.data_ptr(),
-                         group_prefix.data_ptr() if group_prefix is not None else None,
-                         S // n_str, hist_base.data_ptr(), n_str, T, H, Hkv, D, q_out.data_ptr(),
-                         k_hist.data_ptr(), vt_hist.data_ptr(), ldh, _stream())
-    _lib.check(rc, "cs_rope_place" + sfx)
+    if q_out.data_ptr() % 16 or k_hist.data_ptr() % 16 or vt_hist.data_ptr() % 16:
+        raise CSError(f"{name}: q_out, k_hist and vt_hist must be 16-byte aligned")
+    _require_cuda(src, inv_freq, prefix_len, hist_base, q_out, k_hist, vt_hist, group_prefix)
+    rc = getattr(L, name)(*head, inv_freq.data_ptr(), prefix_len.data_ptr(),
+                          group_prefix.data_ptr() if group_prefix is not None else None,
+                          S // n_str, hist_base.data_ptr(), n_str, T, H, Hkv, D, q_out.data_ptr(),
+                          k_hist.data_ptr(), vt_hist.data_ptr(), ldh, _stream())
+    _lib.check(rc, name)
     return q_out
 
 

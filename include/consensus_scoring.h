@@ -471,6 +471,11 @@ int cs_prefix_attention_rows(const void* q, const void* k_prefix, const void* vt
  * k_hist[s][g][j][:] (rotated), vt_hist[s][g][j/32][:][j%32], j = *hist_base + t.  The
  * position of token t of stream s (group i) is prefix_len[group_prefix[i]] + *hist_base + t.
  * bf16 in / out, fp32 rotation.
+ * Refused (CS_ERR_INVALID, nothing launched): ld_hist not a multiple of 32 (the V^T tiles of a
+ * head are whole; the _rows entry points take any ld_hist >= T); q_out, k_hist or vt_hist not
+ * 16-byte aligned; qkv not 8-byte aligned or ld_qkv not a multiple of 4 (head_dim is a
+ * multiple of 8, <= 256).  *hist_base + T <= ld_hist is the caller's to keep: the host does
+ * not read hist_base.
  *
  * Replaces: the per-call re-encoding of the reference's prompts (src/utils.py:249-259):
  *   a candidate token's K/V is computed once and kept for every later step of its stream.

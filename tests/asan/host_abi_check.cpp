@@ -277,6 +277,22 @@ static void check_rejections() {
                                    0.1f, 0.f, 0, nullptr, 0, 0, d, nullptr, 0, nullptr));
   REJECTS(cs_rope_place_rows(nullptr, 64, f, i, nullptr, 1, i, 1, 1, 1, 1, 64, d, d, d, 32, nullptr));
   REJECTS(cs_rope_place_splitk_rows(f, 2, f, i, nullptr, 1, i, 1, 32, 4, 2, 64, d, d, d, 64, nullptr));
+  // blocked V needs whole 32-slot tiles, the outputs 16-byte and the projection 8-byte alignment,
+  // ld_qkv % 4 == 0; the message names the entry point that was called
+  void* d8 = reinterpret_cast<void*>(uintptr_t{264});
+  REJECTS(cs_rope_place(d, 512, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d, d, d, 40, nullptr));
+  CHECK(std::strncmp(cs_last_error(), "cs_rope_place: ", 15) == 0, "names %s", cs_last_error());
+  REJECTS(cs_rope_place_splitk(f, 2, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d, d, d, 40, nullptr));
+  CHECK(std::strncmp(cs_last_error(), "cs_rope_place_splitk: ", 22) == 0, "names %s", cs_last_error());
+  REJECTS(cs_rope_place(d, 512, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d8, d, d, 64, nullptr));
+  REJECTS(cs_rope_place(d, 512, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d, d, d8, 64, nullptr));
+  REJECTS(cs_rope_place_rows(d, 512, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d, d8, d, 40, nullptr));
+  CHECK(std::strncmp(cs_last_error(), "cs_rope_place_rows: ", 20) == 0, "names %s", cs_last_error());
+  REJECTS(cs_rope_place_splitk_rows(f, 2, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d8, d, d, 40, nullptr));
+  CHECK(std::strncmp(cs_last_error(), "cs_rope_place_splitk_rows: ", 27) == 0, "names %s", cs_last_error());
+  REJECTS(cs_rope_place(reinterpret_cast<void*>(uintptr_t{260}), 512, f, i, nullptr, 1, i, 1, 1, 4, 2, 64,
+                        d, d, d, 64, nullptr));
+  REJECTS(cs_rope_place(d, 514, f, i, nullptr, 1, i, 1, 1, 4, 2, 64, d, d, d, 64, nullptr));
   REJECTS(cs_hist_rows_update(i, i, par, i, 4, 32, 0, 4, nullptr));       // source == destination
   REJECTS(cs_hist_rows_update(i, i + 1, par, i, 4, 32, -1, 4, nullptr));  // negative row base
   REJECTS(cs_hist_rows_update(nullptr, i, par, i, 4, 32, 0, 4, nullptr));

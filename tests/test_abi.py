@@ -2,6 +2,7 @@
 header declares, and rejects bad arguments with a status + message (no launch)."""
 import ctypes
 import glob
+import math
 import os
 import re
 
@@ -114,6 +115,88 @@ def test_round4_entry_points_validate_before_launching(pkg):
     assert L.cs_rope_place_splitk(d, 2, d, d, None, 1, d, 1, 1, 4, 2, 40, d, d, d, 32, None) == -1
     assert L.cs_rope_place_splitk(None, 2, d, d, None, 1, d, 1, 1, 4, 2, 64, d, d, d, 32, None) == -1
     assert L.cs_last_error().decode()
+
+
+@pytest.mark.parametrize("entry", ["cs_rope_place", "cs_rope_place_rows", "cs_rope_place_splitk",
+                                   "cs_rope_place_splitk_rows"])
+def test_rope_place_refuses_ragged_tiles_and_misaligned_buffers(pkg, entry):
+    """Blocked V with ld_hist % 32 != 0 (slot 35 of ld_hist 40 would land in the next head's
+    tile), outputs off 16 bytes, a projection off 8 bytes or with ld_qkv % 4 != 0: refused with
+    CS_ERR_INVALID and a message that names the entry point called, before any launch."""
+    from importlib import import_module
+    L = import_module(pkg.__name__ + "._lib").load()
+    d, off8, off4 = ctypes.c_void_p(256), ctypes.c_void_p(264), ctypes.c_void_p(260)
+    fn = getattr(L, entry)
+    splitk, rows = "splitk" in entry, entry.endswith("_rows")
+
+    def call(src=d, ld=512, q=d, k=d, v=d, ldh=64):
+        # one group of one single-token stream, H 4, Hkv 2, D 64: ld_qkv = 8 * 64
+        head = (src, 2) if splitk else (src, ld)
+        return fn(*head, d, d, None, 1, d, 1, 1, 4, 2, 64, q, k, v, ldh, None)
+
+    def refused(what, **kw):
+        assert call(**kw) == -1, what
+        msg = L.cs_last_error().decode()
+        assert msg.startswith(entry + ":") and what in msg, msg
+
+    if not rows:
+        refused("multiple of 32", ldh=40)
+        refused("multiple of 32", ldh=33)
+    refused("16-byte aligned", q=off8)
+    refused("16-byte aligned", k=off8)
+    refused("16-byte aligned", v=off8)
+    if not splitk:
+        refused("8-byte aligned", src=off4)
+        refused("multiple of 4", ld=514)
+        refused("multiple of 4", ld=513)
+
+
+def test_ops_rope_place_mirrors_the_refusals(ops):
+    """ops.rope_place raises on the same conditions before it touches the library's launch, and
+    checks inv_freq for split partials as it does for a bf16 projection."""
+    import torch
+    S, T, H, Hkv, D = 2, 1, 4, 2, 64
+    width = (H + 2 * Hkv) * D
+    bf = torch.bfloat16
+
+    def off(shape, nbytes):
+        n = math.prod(shape)
+        base = torch.zeros(n + 64, dtype=bf)
+        skip = (-base.data_ptr() % 64 + nbytes) // 2
+        t = base[skip:skip + n].view(shape)
+        assert t.data_ptr() % 64 == nbytes
+        return t
+
+    def args(ldh=64, rows=False, **kw):
+        a = dict(qkv=off((S * T, width), 0), inv=torch.zeros(D // 2), plen=torch.zeros(2, dtype=torch.int32),
+                 hb=torch.zeros(1, dtype=torch.int32), q=off((S * T, H, D), 0), k=off((S, Hkv, ldh, D), 0),
+                 v=off((S, Hkv, ldh, D) if rows else (S, Hkv, ldh // 32, D, 32), 0))
+        a.update(kw)
+        return a
+
+    def refused(what, rows=False, **kw):
+        a = args(rows=rows, **kw)
+        with pytest.raises(ops.CSError, match=what):
+            ops.rope_place(a["qkv"], a["inv"], a["plen"], a["hb"], 1, T, H, Hkv, D, a["q"], a["k"], a["v"],
+                           v_rows=rows)
+
+    refused("cs_rope_place: ld_hist must be a multiple of 32", ldh=40)
+    refused("cs_rope_place: q_out, k_hist and vt_hist must be 16-byte aligned", q=off((S * T, H, D), 8))
+    refused("cs_rope_place_rows: q_out, k_hist and vt_hist must be 16-byte aligned", rows=True,
+            k=off((S, Hkv, 64, D), 8))
+    refused("16-byte aligned", v=off((S, Hkv, 2, D, 32), 8))
+    refused("cs_rope_place: qkv must be 8-byte aligned", qkv=off((S * T, width), 4))
+    refused("ld_qkv a multiple of 4", qkv=off((S * T, width + 2), 0)[:, :width])
+    part = ops.SplitPartials(torch.zeros(2, S * T, width))
+    refused("inv_freq must be float32", qkv=part, inv=torch.zeros(D // 2, dtype=torch.float64))
+    refused("inv_freq must be float32", qkv=part, inv=torch.zeros(D))
+    refused("cs_rope_place_splitk: ld_hist must be a multiple of 32", qkv=part, ldh=40)
+    refused("cs_rope_place_splitk_rows: q_out", qkv=part, rows=True, q=off((S * T, H, D), 8))
+    # a row-layout history of any length passes these checks: the next refusal is the device's
+    with pytest.raises(ops.CSError, match="CPU tensor"):
+        a = args(ldh=40, rows=True)
+        ops.rope_place(a["qkv"], a["inv"], a["plen"], a["hb"], 1, T, H, Hkv, D, a["q"], a["k"], a["v"],
+                       v_rows=True)
 
 
 def test_missing_library_raises(pkg, monkeypatch, tmp_path):
