@@ -42,6 +42,8 @@ EXPORTED = (
     "cs_sample_step_workspace_size", "cs_sample_step",
     "cs_vocab_sample_ex_workspace_size", "cs_vocab_sample_ex",
     "cs_sample_step_ex_workspace_size", "cs_sample_step_ex",
+    "cs_dfa_token_masks", "cs_vocab_sample_dfa_workspace_size", "cs_vocab_sample_dfa",
+    "cs_sample_step_dfa_workspace_size", "cs_sample_step_dfa",
     "cs_embed_layer_norm", "cs_add_layer_norm", "cs_gelu", "cs_encoder_attention",
     "cs_cosine_welfare",
     "cs_standardize_workspace_size", "cs_standardize", "cs_kmeans_workspace_size",
@@ -204,6 +206,20 @@ def load():
                                     f32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp,
                                     vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     L.cs_sample_step_ex.restype = ctypes.c_int
+    L.cs_dfa_token_masks.argtypes = [vp, vp, i32, vp, vp, i64, vp, i32, vp, vp]
+    L.cs_dfa_token_masks.restype = ctypes.c_int
+    L.cs_vocab_sample_dfa_workspace_size.argtypes = [i64, i64, i32]
+    L.cs_vocab_sample_dfa_workspace_size.restype = ctypes.c_size_t
+    L.cs_vocab_sample_dfa.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, i32, vp, i32, f32,
+                                      f32, vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.cs_vocab_sample_dfa.restype = ctypes.c_int
+    L.cs_sample_step_dfa_workspace_size.argtypes = [i64, i64]
+    L.cs_sample_step_dfa_workspace_size.restype = ctypes.c_size_t
+    L.cs_sample_step_dfa.argtypes = [vp, ctypes.c_int, i64, i64, i64, f32, f32, vp, vp, vp, i32, f32,
+                                     f32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i64, vp,
+                                     i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                     vp]
+    L.cs_sample_step_dfa.restype = ctypes.c_int
     L.cs_embed_layer_norm.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, i32, vp, vp, vp, i64, f32,
                                       vp, i64, vp, vp]
     L.cs_embed_layer_norm.restype = ctypes.c_int

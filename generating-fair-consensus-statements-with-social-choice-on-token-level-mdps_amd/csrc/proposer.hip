@@ -157,7 +157,10 @@ __device__ __forceinline__ void draw_merge(float& s, int32_t& i, float s2, int32
 // the vocabulary.  1 (cs_sample_step with a bias list): the listed tokens take bias_value in
 // fp32 before the soft-cap.  2 (the *_ex entries): a second bitmap marks the row's seen tokens,
 // which take the repetition penalty after the soft-cap, and with `greedy` the score is the
-// transformed logit itself (no seed read, no Gumbel noise).
+// transformed logit itself (no seed read, no Gumbel noise).  3 (the *_dfa entries): the two
+// bitmaps of 2, and one bit per token read from GLOBAL memory -- row dfa_state[row] of the
+// automaton's token masks -- whose clear bit makes the transformed logit -inf: out of the
+// log-sum-exp and, by the never-drawn rule, out of the draw.
 struct StepIn {
   const int32_t* step;
   const int32_t* done;
@@ -172,6 +175,10 @@ struct StepIn {
   int32_t max_tokens;
   float penalty;               // 1: off, the seen set is not looked at
   int32_t greedy;
+  // the *_dfa entries only
+  const uint32_t* masks;       // [n_states][mask_words], bit v of row q: token v drawable in q
+  const int32_t* dfa_state;    // per row; a state outside [0, n_states) allows nothing
+  int32_t mask_words, n_states;
 };
 constexpr unsigned long long kSeedMul = 1000003ull;   // runtime.draw_seed
 constexpr int64_t kMaxBiasSlice = 1 << 19;            // bitmap <= 64 KB of LDS
@@ -247,11 +254,12 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
   const int64_t v1 = min(vocab, v0 + split_len);
   const int nw = static_cast<int>((v1 - v0 + 31) >> 5);
   uint32_t* sm_seen = sm_bias + nw;
+  constexpr int kBitmaps = TABLES > 2 ? 2 : TABLES;
   if (TABLES > 0) {
-    for (int w = tid; w < TABLES * nw; w += 256) sm_bias[w] = 0u;
+    for (int w = tid; w < kBitmaps * nw; w += 256) sm_bias[w] = 0u;
     __syncthreads();
     for (int j = tid; j < in.n_bias; j += 256) mark(sm_bias, in.bias_ids[j], v0, v1);
-    if (TABLES == 2 && in.penalty != 1.0f) {
+    if (TABLES >= 2 && in.penalty != 1.0f) {
       if (in.seen_off) {
         const int64_t b = in.seen_off[row + 1];
         for (int64_t j = in.seen_off[row] + tid; j < b; j += 256)
@@ -265,7 +273,12 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
     }
     __syncthreads();
   }
-  const bool greedy = TABLES == 2 && in.greedy != 0;
+  const bool greedy = TABLES >= 2 && in.greedy != 0;
+  const uint32_t* allow = nullptr;   // TABLES == 3: the mask row of the row's state
+  if (TABLES == 3) {
+    const int32_t q = in.dfa_state[row];
+    if (q >= 0 && q < in.n_states) allow = in.masks + static_cast<int64_t>(q) * in.mask_words;
+  }
   unsigned long long sd[kMaxDraws];
   float bs[kMaxDraws];
   int32_t bi[kMaxDraws];
@@ -281,8 +294,12 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
   bool saw_nan = false;
   for (int64_t v = v0 + tid; v < v1; v += 256) {
     const bool biased = TABLES > 0 && marked(sm_bias, v - v0);
-    const bool seen = TABLES == 2 && marked(sm_seen, v - v0);
-    const float y = ex_logit<DT, CAP>(rp, v, biased, seen, in, cap, inv_cap) * inv_temp;
+    const bool seen = TABLES >= 2 && marked(sm_seen, v - v0);
+    // a clear bit: the logit is not loaded at all (measured 1.5 us per step cheaper at 64 x
+    // 128,256 than loading it beside the mask word and discarding it)
+    const bool dead = TABLES == 3 && !(allow && ((allow[v >> 5] >> (v & 31)) & 1u));
+    const float y =
+        dead ? -INFINITY : ex_logit<DT, CAP>(rp, v, biased, seen, in, cap, inv_cap) * inv_temp;
     saw_nan |= y != y;
     lse_accum<1>(m, s, &y);
 #pragma unroll
@@ -407,6 +424,7 @@ __global__ __launch_bounds__(64) void vocab_sample_merge_kernel(
 
 // The stop strings of cs_sample_step_ex, passed by value: the bytes of string k are
 // bytes[off[k] : off[k+1]], at most kMaxStopSeq strings of at most kMaxStopLen bytes.
+constexpr int kMaxDfaStates = 1024;   // cs_dfa_token_masks and the *_dfa entries
 constexpr int kMaxStopSeq = 8;
 constexpr int kMaxStopLen = 32;
 struct StopSeqs {
@@ -417,8 +435,23 @@ struct StopSeqs {
   int32_t n_seq;
   int32_t off[kMaxStopSeq + 1];
   uint8_t bytes[kMaxStopSeq * kMaxStopLen];
+  // cs_sample_step_dfa: the automaton an appended token's bytes are walked through
+  const int16_t* trans;       // [n_states][256], -1 dead; NULL: no automaton
+  int32_t* dfa_state;         // [S]
+  int32_t n_states;
 };
 struct NoStopSeqs {};
+
+// The state after token i's bytes from state q: -1 once a byte has no transition (or q is no
+// state), q itself for a token with no bytes.
+__device__ __forceinline__ int32_t dfa_walk(const StopSeqs& sq, int32_t q, int32_t i) {
+  const int32_t t0 = sq.tok_off[i], t1 = sq.tok_off[i + 1];
+  for (int32_t p = t0; p < t1; ++p) {
+    if (q < 0 || q >= sq.n_states) return -1;
+    q = sq.trans[q * 256 + sq.tok_bytes[p]];
+  }
+  return (q < 0 || q >= sq.n_states) ? -1 : q;
+}
 
 // Wave-wide, after token i was appended to stream `row`: does a stop string end inside the
 // token's bytes in the window tail ++ bytes(i)?  Lanes take the end positions; every byte of
@@ -504,6 +537,8 @@ __global__ __launch_bounds__(64) void sample_step_merge_kernel(
       }
     }
     if constexpr (EX) {
+      if (sq.trans && lane == 0 && appended != 0)
+        sq.dfa_state[row] = dfa_walk(sq, sq.dfa_state[row], i);
       if (sq.n_seq > 0 && __shfl(appended, 0, 64) != 0) {   // wave-uniform
         if (stop_window(sq, row, i, lane) && lane == 0) {
           done[row] = 1;   // the token stays appended: the host's cut sees the whole occurrence
@@ -584,13 +619,15 @@ int plan_sample(SampleCall& c, const char* fn, const void* logits, int dtype, in
 // so the limit is raised before it is met.
 template <int DT, bool CAP, bool STEP, int TABLES>
 void launch_stream(const SampleCall& c, const StepIn& in) {
-  const size_t lds = TABLES * static_cast<size_t>((c.plan.split_len + 31) / 32) * sizeof(uint32_t);
+  const size_t lds =
+      (TABLES > 2 ? 2 : TABLES) * static_cast<size_t>((c.plan.split_len + 31) / 32) * sizeof(uint32_t);
   launch_big_lds<&vocab_sample_kernel<DT, CAP, STEP, TABLES>, 60 * 1024>(
       kExLdsLimit, dim3(c.grid), dim3(256), lds, c.st, c.lg, c.vocab, c.ld_bytes, c.plan.nsplit,
       c.plan.split_len, c.inv_t, c.cap, c.inv_cap, c.seeds, c.n_draw, c.lse_part, c.draw_part, in);
 }
 
-// both stages of the plain entries (TABLES 0: cs_vocab_sample, 2: cs_vocab_sample_ex)
+// both stages of the plain entries (TABLES 0: cs_vocab_sample, 2: cs_vocab_sample_ex,
+// 3: cs_vocab_sample_dfa; a drawn token's bit is set, so the merge stage is that of 2)
 template <int TABLES>
 int launch_plain(const char* fn, const SampleCall& c, const StepIn& in, int32_t* out_ids,
                  float* out_lp) {
@@ -598,7 +635,7 @@ int launch_plain(const char* fn, const SampleCall& c, const StepIn& in, int32_t*
     constexpr int DT = decltype(dt)::value;
     constexpr bool CAP = decltype(cap)::value;
     launch_stream<DT, CAP, false, TABLES>(c, in);
-    hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP, TABLES == 2>), dim3(c.rows), dim3(64), 0,
+    hipLaunchKernelGGL((vocab_sample_merge_kernel<DT, CAP, TABLES >= 2>), dim3(c.rows), dim3(64), 0,
                        c.st, c.lg, c.ld_bytes, c.plan.nsplit, c.inv_t, c.cap, c.inv_cap, c.lse_part,
                        c.draw_part, c.n_draw, out_ids, out_lp, in);
   });
@@ -634,7 +671,8 @@ bool step_ptr_missing(const void* logits, const uint64_t* base_seeds, bool greed
          (s.n_stop > 0 && !s.stop_ids);
 }
 
-// both stages of the step entries (TABLES 0 or 1: cs_sample_step, 2: cs_sample_step_ex)
+// both stages of the step entries (TABLES 0 or 1: cs_sample_step, 2: cs_sample_step_ex,
+// 3: cs_sample_step_dfa)
 template <int TABLES, typename Seqs>
 int launch_step(const char* fn, const SampleCall& c, const StepIn& in, const StepState& s,
                 const Seqs& sq) {
@@ -642,7 +680,7 @@ int launch_step(const char* fn, const SampleCall& c, const StepIn& in, const Ste
     constexpr int DT = decltype(dt)::value;
     constexpr bool CAP = decltype(cap)::value;
     launch_stream<DT, CAP, true, TABLES>(c, in);
-    hipLaunchKernelGGL((sample_step_merge_kernel<DT, CAP, TABLES == 2>), dim3(c.rows), dim3(64), 0,
+    hipLaunchKernelGGL((sample_step_merge_kernel<DT, CAP, TABLES >= 2>), dim3(c.rows), dim3(64), 0,
                        c.st, c.lg, c.ld_bytes, c.plan.nsplit, c.inv_t, c.cap, c.inv_cap, c.lse_part,
                        c.draw_part, in, s.stop_ids, s.n_stop, s.max_tokens, s.pad_id, s.done,
                        s.out_len, s.out_tokens, s.out_lp, reinterpret_cast<long long*>(s.next_tok),
@@ -660,6 +698,178 @@ int check_controls(const char* fn, float temperature, float penalty, int32_t n_b
   if (n_bias < 0 || n_bias > 1024)
     return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 <= n_bias <= 1024");
   return CS_OK;
+}
+
+// The automaton arguments of the *_dfa entries (masks != NULL), checked by check_dfa.
+struct DfaArgs {
+  const uint32_t* masks;
+  int64_t mask_words;
+  int32_t n_states;
+  const int32_t* state;    // plain entry: read; step entry: read and advanced
+  const int16_t* trans;    // step entry only
+};
+
+int check_dfa(const char* fn, const DfaArgs& d, int64_t vocab, bool step, const void* tok_bytes,
+              const void* tok_off) {
+  if (d.n_states < 1 || d.n_states > kMaxDfaStates)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need 1 <= n_states <= 1024");
+  if (d.mask_words < (vocab + 31) / 32 || d.mask_words > INT32_MAX)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": mask_words below ceil(vocab / 32)");
+  if (!d.state || (step && (!d.trans || !tok_bytes || !tok_off)))
+    return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
+  return CS_OK;
+}
+
+void set_dfa(StepIn& in, const DfaArgs& d) {
+  in.masks = d.masks;
+  in.dfa_state = d.state;
+  in.mask_words = static_cast<int32_t>(d.mask_words);
+  in.n_states = d.n_states;
+}
+
+// cs_dfa_token_masks: one thread per (state, token), a wave's ballot is two mask words.
+__global__ __launch_bounds__(256) void dfa_token_masks_kernel(
+    const int16_t* __restrict__ trans, const uint8_t* __restrict__ accept, int32_t n_states,
+    const uint8_t* __restrict__ tok_bytes, const int32_t* __restrict__ tok_off, int64_t vocab,
+    int64_t words, const int32_t* __restrict__ stop_ids, int32_t n_stop,
+    uint32_t* __restrict__ masks) {
+  const int32_t q0 = blockIdx.y;
+  const int64_t v = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  bool alive = false;
+  if (v < vocab) {
+    bool is_stop = false;
+    for (int j = 0; j < n_stop; ++j) is_stop |= stop_ids[j] == v;
+    if (is_stop) {
+      alive = accept[q0] != 0;
+    } else {
+      const int32_t t0 = tok_off[v], t1 = tok_off[v + 1];
+      int32_t q = q0;
+      for (int32_t p = t0; p < t1 && q >= 0; ++p) {
+        q = trans[q * 256 + tok_bytes[p]];
+        if (q >= n_states) q = -1;   // no state: a malformed table reads nothing out of bounds
+      }
+      alive = t1 > t0 && q >= 0;
+    }
+  }
+  const unsigned long long bits = __ballot(alive);
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (v - lane) >> 5;   // the wave's first word
+  if (lane == 0 && w < words) masks[q0 * words + w] = static_cast<uint32_t>(bits);
+  if (lane == 32 && w + 1 < words) masks[q0 * words + w + 1] = static_cast<uint32_t>(bits >> 32);
+}
+
+// cs_vocab_sample_ex (dfa NULL) and cs_vocab_sample_dfa with masks
+int vocab_sample_ex_body(const char* fn, const void* logits, int dtype, int64_t rows, int64_t vocab,
+                         int64_t ld, float temperature, float softcap, const uint64_t* seeds,
+                         int32_t n_draw, const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                         float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                         const DfaArgs* dfa, int32_t* out_ids, float* out_lp, void* workspace,
+                         size_t workspace_bytes, cs_stream_t stream) {
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  if (rows < 0 || n_draw <= 0 || n_draw > kMaxDraws)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need rows >= 0 and 0 < n_draw <= 16");
+  if (int rc = check_controls(fn, temperature, repetition_penalty, n_bias)) return rc;
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  if (dfa)
+    if (int rc = check_dfa(fn, *dfa, vocab, false, nullptr, nullptr)) return rc;
+  if (rows == 0) return CS_OK;
+  const bool greedy = temperature == 0.0f;
+  const bool penalised = repetition_penalty != 1.0f && seen_off != nullptr;
+  if (!logits || !out_ids || (!greedy && !seeds) || (n_bias > 0 && !bias_ids) ||
+      (seen_off && !seen_ids))
+    return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
+  if (!dfa && !greedy && !penalised && n_bias == 0)   // every control off: the old entry, its kernels
+    return cs_vocab_sample(logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
+                           out_ids, out_lp, workspace, workspace_bytes, stream);
+  SampleCall c;
+  if (int rc = plan_sample(c, fn, logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
+                           workspace, workspace_bytes, false,
+                           ": a biased or penalised row slice exceeds 2^19 tokens", stream))
+    return rc;
+  StepIn in{};
+  in.bias_ids = bias_ids;
+  in.n_bias = n_bias;
+  in.bias_value = bias_value;
+  in.seen_ids = penalised ? seen_ids : nullptr;
+  in.seen_off = penalised ? seen_off : nullptr;
+  in.penalty = penalised ? repetition_penalty : 1.0f;
+  in.greedy = greedy;
+  if (!dfa) return launch_plain<2>(fn, c, in, out_ids, out_lp);
+  set_dfa(in, *dfa);
+  return launch_plain<3>(fn, c, in, out_ids, out_lp);
+}
+
+// cs_sample_step_ex (dfa NULL) and cs_sample_step_dfa with masks
+int sample_step_ex_body(const char* fn, const void* logits, int dtype, int64_t S, int64_t vocab,
+                        int64_t ld, float temperature, float softcap, const uint64_t* base_seeds,
+                        const int32_t* step, const int32_t* bias_ids, int32_t n_bias,
+                        float bias_value, float repetition_penalty, const int32_t* seen_ids,
+                        const int32_t* seen_off, const int32_t* stop_ids, int32_t n_stop,
+                        const uint8_t* tok_bytes, const int32_t* tok_off, const uint8_t* stop_bytes,
+                        const int32_t* stop_off, int32_t n_stop_seq, uint8_t* tail, int32_t* tail_len,
+                        const DfaArgs* dfa, int32_t* dfa_state, int32_t max_tokens, int32_t pad_id,
+                        int32_t* done, int32_t* out_len, int32_t* out_tokens, float* out_lp,
+                        int64_t* next_tok, int32_t* n_alive, void* workspace, size_t workspace_bytes,
+                        cs_stream_t stream) {
+  StepIn in{step, done, bias_ids, n_bias, bias_value};
+  const StepState state{stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
+                        next_tok, n_alive};
+  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
+  const char* bad_counts =
+      (n_stop < 0 || n_stop > 16) ? ": need 0 <= n_stop <= 16"
+      : (n_stop_seq < 0 || n_stop_seq > kMaxStopSeq) ? ": need 0 <= n_stop_seq <= 8" : nullptr;
+  if (int rc = check_step_state(fn, S, vocab, state, bad_counts)) return rc;
+  if (int rc = check_controls(fn, temperature, repetition_penalty, n_bias)) return rc;
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  if (dfa)
+    if (int rc = check_dfa(fn, *dfa, vocab, true, tok_bytes, tok_off)) return rc;
+  StopSeqs sq{};
+  if (n_stop_seq > 0) {
+    if (!stop_bytes || !stop_off) return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
+    for (int k = 0; k < n_stop_seq; ++k) {   // stop_bytes / stop_off are host memory
+      const int64_t len = static_cast<int64_t>(stop_off[k + 1]) - stop_off[k];
+      if (stop_off[0] != 0 || len < 1 || len > kMaxStopLen)
+        return fail(CS_ERR_INVALID, std::string(fn) + ": a stop string needs 1 to 32 bytes");
+    }
+    sq.n_seq = n_stop_seq;
+    for (int k = 0; k <= n_stop_seq; ++k) sq.off[k] = stop_off[k];
+    for (int j = 0; j < stop_off[n_stop_seq]; ++j) sq.bytes[j] = stop_bytes[j];
+    sq.tail = tail;
+    sq.tail_len = tail_len;
+  }
+  if (n_stop_seq > 0 || dfa) {
+    sq.tok_bytes = tok_bytes;
+    sq.tok_off = tok_off;
+  }
+  if (S == 0) return CS_OK;
+  const bool greedy = temperature == 0.0f;
+  const bool penalised = repetition_penalty != 1.0f;
+  if (step_ptr_missing(logits, base_seeds, greedy, in, state) || (seen_off && !seen_ids) ||
+      (n_stop_seq > 0 && (!tok_bytes || !tok_off || !tail || !tail_len)))
+    return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
+  if (!dfa && !greedy && !penalised && n_stop_seq == 0)   // every control off: the old entry, its kernels
+    return cs_sample_step(logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, step,
+                          bias_ids, n_bias, bias_value, stop_ids, n_stop, max_tokens, pad_id, done,
+                          out_len, out_tokens, out_lp, next_tok, n_alive, workspace, workspace_bytes,
+                          stream);
+  SampleCall c;
+  if (int rc = plan_sample(c, fn, logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, 1,
+                           workspace, workspace_bytes, true,
+                           ": a biased or penalised row slice exceeds 2^19 tokens", stream))
+    return rc;
+  in.seen_ids = penalised ? seen_ids : nullptr;
+  in.seen_off = penalised ? seen_off : nullptr;
+  in.out_tokens = out_tokens;
+  in.out_len = out_len;
+  in.max_tokens = max_tokens;
+  in.penalty = repetition_penalty;
+  in.greedy = greedy;
+  if (!dfa) return launch_step<2>(fn, c, in, state, sq);
+  set_dfa(in, *dfa);
+  sq.trans = dfa->trans;
+  sq.dfa_state = dfa_state;
+  sq.n_states = dfa->n_states;
+  return launch_step<3>(fn, c, in, state, sq);
 }
 
 }  // namespace
@@ -782,35 +992,10 @@ int cs_vocab_sample_ex(const void* logits, int dtype, int64_t rows, int64_t voca
                        float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
                        int32_t* out_ids, float* out_lp, void* workspace, size_t workspace_bytes,
                        cs_stream_t stream) {
-  const char* fn = "cs_vocab_sample_ex";
-  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
-  if (rows < 0 || n_draw <= 0 || n_draw > kMaxDraws)
-    return fail(CS_ERR_INVALID, std::string(fn) + ": need rows >= 0 and 0 < n_draw <= 16");
-  if (int rc = check_controls(fn, temperature, repetition_penalty, n_bias)) return rc;
-  if (int rc = check_softcap(fn, softcap)) return rc;
-  if (rows == 0) return CS_OK;
-  const bool greedy = temperature == 0.0f;
-  const bool penalised = repetition_penalty != 1.0f && seen_off != nullptr;
-  if (!logits || !out_ids || (!greedy && !seeds) || (n_bias > 0 && !bias_ids) ||
-      (seen_off && !seen_ids))
-    return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
-  if (!greedy && !penalised && n_bias == 0)   // every control off: the old entry, its kernels
-    return cs_vocab_sample(logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
-                           out_ids, out_lp, workspace, workspace_bytes, stream);
-  SampleCall c;
-  if (int rc = plan_sample(c, fn, logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
-                           workspace, workspace_bytes, false,
-                           ": a biased or penalised row slice exceeds 2^19 tokens", stream))
-    return rc;
-  StepIn in{};
-  in.bias_ids = bias_ids;
-  in.n_bias = n_bias;
-  in.bias_value = bias_value;
-  in.seen_ids = penalised ? seen_ids : nullptr;
-  in.seen_off = penalised ? seen_off : nullptr;
-  in.penalty = penalised ? repetition_penalty : 1.0f;
-  in.greedy = greedy;
-  return launch_plain<2>(fn, c, in, out_ids, out_lp);
+  return vocab_sample_ex_body("cs_vocab_sample_ex", logits, dtype, rows, vocab, ld, temperature,
+                              softcap, seeds, n_draw, bias_ids, n_bias, bias_value,
+                              repetition_penalty, seen_ids, seen_off, nullptr, out_ids, out_lp,
+                              workspace, workspace_bytes, stream);
 }
 
 size_t cs_sample_step_ex_workspace_size(int64_t S, int64_t vocab) {
@@ -827,57 +1012,86 @@ int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, i
                       int32_t pad_id, int32_t* done, int32_t* out_len, int32_t* out_tokens,
                       float* out_lp, int64_t* next_tok, int32_t* n_alive, void* workspace,
                       size_t workspace_bytes, cs_stream_t stream) {
-  const char* fn = "cs_sample_step_ex";
-  StepIn in{step, done, bias_ids, n_bias, bias_value};
-  const StepState state{stop_ids, n_stop, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
-                        next_tok, n_alive};
-  if (int rc = check_logits(fn, dtype, vocab, ld)) return rc;
-  const char* bad_counts =
-      (n_stop < 0 || n_stop > 16) ? ": need 0 <= n_stop <= 16"
-      : (n_stop_seq < 0 || n_stop_seq > kMaxStopSeq) ? ": need 0 <= n_stop_seq <= 8" : nullptr;
-  if (int rc = check_step_state(fn, S, vocab, state, bad_counts)) return rc;
-  if (int rc = check_controls(fn, temperature, repetition_penalty, n_bias)) return rc;
-  if (int rc = check_softcap(fn, softcap)) return rc;
-  StopSeqs sq{};
-  if (n_stop_seq > 0) {
-    if (!stop_bytes || !stop_off) return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
-    for (int k = 0; k < n_stop_seq; ++k) {   // stop_bytes / stop_off are host memory
-      const int64_t len = static_cast<int64_t>(stop_off[k + 1]) - stop_off[k];
-      if (stop_off[0] != 0 || len < 1 || len > kMaxStopLen)
-        return fail(CS_ERR_INVALID, std::string(fn) + ": a stop string needs 1 to 32 bytes");
-    }
-    sq.n_seq = n_stop_seq;
-    for (int k = 0; k <= n_stop_seq; ++k) sq.off[k] = stop_off[k];
-    for (int j = 0; j < stop_off[n_stop_seq]; ++j) sq.bytes[j] = stop_bytes[j];
-    sq.tok_bytes = tok_bytes;
-    sq.tok_off = tok_off;
-    sq.tail = tail;
-    sq.tail_len = tail_len;
-  }
-  if (S == 0) return CS_OK;
-  const bool greedy = temperature == 0.0f;
-  const bool penalised = repetition_penalty != 1.0f;
-  if (step_ptr_missing(logits, base_seeds, greedy, in, state) || (seen_off && !seen_ids) ||
-      (n_stop_seq > 0 && (!tok_bytes || !tok_off || !tail || !tail_len)))
+  return sample_step_ex_body("cs_sample_step_ex", logits, dtype, S, vocab, ld, temperature, softcap,
+                             base_seeds, step, bias_ids, n_bias, bias_value, repetition_penalty,
+                             seen_ids, seen_off, stop_ids, n_stop, tok_bytes, tok_off, stop_bytes,
+                             stop_off, n_stop_seq, tail, tail_len, nullptr, nullptr, max_tokens,
+                             pad_id, done, out_len, out_tokens, out_lp, next_tok, n_alive, workspace,
+                             workspace_bytes, stream);
+}
+
+int cs_dfa_token_masks(const int16_t* trans, const uint8_t* accept, int32_t n_states,
+                       const uint8_t* tok_bytes, const int32_t* tok_off, int64_t vocab,
+                       const int32_t* stop_ids, int32_t n_stop, uint32_t* masks,
+                       cs_stream_t stream) {
+  const char* fn = "cs_dfa_token_masks";
+  if (n_states < 1 || n_states > kMaxDfaStates)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need 1 <= n_states <= 1024");
+  if (vocab <= 0 || vocab > INT32_MAX)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 < vocab < 2^31");
+  if (n_stop < 0 || n_stop > 16)
+    return fail(CS_ERR_INVALID, std::string(fn) + ": need 0 <= n_stop <= 16");
+  if (!trans || !accept || !tok_bytes || !tok_off || !masks || (n_stop > 0 && !stop_ids))
     return fail(CS_ERR_INVALID, std::string(fn) + ": NULL pointer");
-  if (!greedy && !penalised && n_stop_seq == 0)   // every control off: the old entry, its kernels
-    return cs_sample_step(logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, step,
-                          bias_ids, n_bias, bias_value, stop_ids, n_stop, max_tokens, pad_id, done,
-                          out_len, out_tokens, out_lp, next_tok, n_alive, workspace, workspace_bytes,
-                          stream);
-  SampleCall c;
-  if (int rc = plan_sample(c, fn, logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, 1,
-                           workspace, workspace_bytes, true,
-                           ": a biased or penalised row slice exceeds 2^19 tokens", stream))
-    return rc;
-  in.seen_ids = penalised ? seen_ids : nullptr;
-  in.seen_off = penalised ? seen_off : nullptr;
-  in.out_tokens = out_tokens;
-  in.out_len = out_len;
-  in.max_tokens = max_tokens;
-  in.penalty = repetition_penalty;
-  in.greedy = greedy;
-  return launch_step<2>(fn, c, in, state, sq);
+  const int64_t words = (vocab + 31) / 32;
+  hipLaunchKernelGGL(dfa_token_masks_kernel,
+                     dim3(static_cast<uint32_t>((vocab + 255) / 256), static_cast<uint32_t>(n_states)),
+                     dim3(256), 0, static_cast<hipStream_t>(stream), trans, accept, n_states,
+                     tok_bytes, tok_off, vocab, words, stop_ids, n_stop, masks);
+  return check_launch(fn);
+}
+
+size_t cs_vocab_sample_dfa_workspace_size(int64_t rows, int64_t vocab, int32_t n_draw) {
+  return cs_vocab_sample_workspace_size(rows, vocab, n_draw);
+}
+
+int cs_vocab_sample_dfa(const void* logits, int dtype, int64_t rows, int64_t vocab, int64_t ld,
+                        float temperature, float softcap, const uint64_t* seeds, int32_t n_draw,
+                        const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                        float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                        const uint32_t* masks, int64_t mask_words, int32_t n_states,
+                        const int32_t* dfa_state, int32_t* out_ids, float* out_lp, void* workspace,
+                        size_t workspace_bytes, cs_stream_t stream) {
+  if (!masks)   // no automaton: the old entry, its kernels
+    return cs_vocab_sample_ex(logits, dtype, rows, vocab, ld, temperature, softcap, seeds, n_draw,
+                              bias_ids, n_bias, bias_value, repetition_penalty, seen_ids, seen_off,
+                              out_ids, out_lp, workspace, workspace_bytes, stream);
+  const DfaArgs dfa{masks, mask_words, n_states, dfa_state, nullptr};
+  return vocab_sample_ex_body("cs_vocab_sample_dfa", logits, dtype, rows, vocab, ld, temperature,
+                              softcap, seeds, n_draw, bias_ids, n_bias, bias_value,
+                              repetition_penalty, seen_ids, seen_off, &dfa, out_ids, out_lp,
+                              workspace, workspace_bytes, stream);
+}
+
+size_t cs_sample_step_dfa_workspace_size(int64_t S, int64_t vocab) {
+  return cs_sample_step_workspace_size(S, vocab);
+}
+
+int cs_sample_step_dfa(const void* logits, int dtype, int64_t S, int64_t vocab, int64_t ld,
+                       float temperature, float softcap, const uint64_t* base_seeds,
+                       const int32_t* step, const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                       float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                       const int32_t* stop_ids, int32_t n_stop, const uint8_t* tok_bytes,
+                       const int32_t* tok_off, const uint8_t* stop_bytes, const int32_t* stop_off,
+                       int32_t n_stop_seq, uint8_t* tail, int32_t* tail_len, const uint32_t* masks,
+                       int64_t mask_words, const int16_t* trans, int32_t n_states,
+                       int32_t* dfa_state, int32_t max_tokens, int32_t pad_id, int32_t* done,
+                       int32_t* out_len, int32_t* out_tokens, float* out_lp, int64_t* next_tok,
+                       int32_t* n_alive, void* workspace, size_t workspace_bytes,
+                       cs_stream_t stream) {
+  if (!masks)   // no automaton: the old entry, its kernels
+    return cs_sample_step_ex(logits, dtype, S, vocab, ld, temperature, softcap, base_seeds, step,
+                             bias_ids, n_bias, bias_value, repetition_penalty, seen_ids, seen_off,
+                             stop_ids, n_stop, tok_bytes, tok_off, stop_bytes, stop_off, n_stop_seq,
+                             tail, tail_len, max_tokens, pad_id, done, out_len, out_tokens, out_lp,
+                             next_tok, n_alive, workspace, workspace_bytes, stream);
+  const DfaArgs dfa{masks, mask_words, n_states, dfa_state, trans};
+  return sample_step_ex_body("cs_sample_step_dfa", logits, dtype, S, vocab, ld, temperature, softcap,
+                             base_seeds, step, bias_ids, n_bias, bias_value, repetition_penalty,
+                             seen_ids, seen_off, stop_ids, n_stop, tok_bytes, tok_off, stop_bytes,
+                             stop_off, n_stop_seq, tail, tail_len, &dfa, dfa_state, max_tokens,
+                             pad_id, done, out_len, out_tokens, out_lp, next_tok, n_alive, workspace,
+                             workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -603,13 +603,17 @@ def sample_step_ex(logits: torch.Tensor, base_seeds: Optional[torch.Tensor], ste
                    tok_off: Optional[torch.Tensor] = None, tail: Optional[torch.Tensor] = None,
                    tail_len: Optional[torch.Tensor] = None,
                    out_lp: Optional[torch.Tensor] = None, max_tokens: Optional[int] = None,
-                   vocab: Optional[int] = None, workspace: Optional[Workspace] = None) -> None:
+                   vocab: Optional[int] = None, workspace: Optional[Workspace] = None,
+                   _dfa=None) -> None:
     """``sample_step`` with the controls of cs_sample_step_ex: temperature 0 is greedy, the
     tokens of seen_ids[seen_off[s]:seen_off[s+1]] and the stream's own out_tokens take the
     repetition penalty, and stop_seqs (a sequence of bytes objects, held by the host) end a
     stream whose decoded bytes complete one: tok_bytes (uint8) / tok_off (int32 [vocab + 1])
     are the tokens' bytes, tail (uint8 [S, 32]) / tail_len (int32 [S]) the per-stream window,
-    zero at the start.  With every control off this is ``sample_step``, bit for bit."""
+    zero at the start.  With every control off this is ``sample_step``, bit for bit.
+    (``_dfa`` is sample_step_dfa's way in: the same body around cs_sample_step_dfa.)"""
+    entry = "cs_sample_step_ex" if _dfa is None else "cs_sample_step_dfa"
+    dfa_tensors = () if _dfa is None else _dfa[:3]
     stop_seqs = [bytes(b) for b in stop_seqs]
     offs = [0]
     for b in stop_seqs:
@@ -626,12 +630,108 @@ def sample_step_ex(logits: torch.Tensor, base_seeds: Optional[torch.Tensor], ste
                 _state_ptr(tok_off, "tok_off", torch.int32, (vocab + 1,)),
                 ctypes.cast(stop_bytes, ctypes.c_void_p), ctypes.cast(stop_off, ctypes.c_void_p),
                 len(stop_seqs), _state_ptr(tail, "tail", torch.uint8, (S, MAX_STOP_LEN)),
-                _state_ptr(tail_len, "tail_len", torch.int32, (S,)))
+                _state_ptr(tail_len, "tail_len", torch.int32, (S,)), *dfa_args(S))
 
-    _sample_step("cs_sample_step_ex", logits, base_seeds, step, done, out_len, out_tokens, next_tok,
+    def dfa_args(S):
+        # cs_sample_step_dfa: masks, mask_words, trans, n_states, dfa_state
+        if _dfa is None:
+            return ()
+        masks, trans, dfa_state, n_states = _dfa
+        mp, words, n, sp = _mask_args(masks, dfa_state, S, n_states)
+        return mp, words, _ptr(trans) if masks is not None else None, n, sp
+
+    _sample_step(entry, logits, base_seeds, step, done, out_len, out_tokens, next_tok,
                  n_alive, pad_id, temperature, softcap, bias_ids, bias_value, stop_ids, out_lp,
-                 max_tokens, vocab, workspace, (seen_ids, seen_off, tok_bytes, tok_off, tail, tail_len),
+                 max_tokens, vocab, workspace,
+                 (seen_ids, seen_off, tok_bytes, tok_off, tail, tail_len, *dfa_tensors),
                  penalty, seq_args)
+
+
+MAX_DFA_STATES = 1024                  # cs_dfa_token_masks, cs_vocab_sample_dfa, cs_sample_step_dfa
+
+
+def dfa_token_masks(trans: torch.Tensor, accept: torch.Tensor, tok_bytes: torch.Tensor,
+                    tok_off: torch.Tensor, stop_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-state token masks of a byte automaton (cs_dfa_token_masks): trans int16
+    [n_states, 256] (-1 dead), accept uint8 [n_states], tok_bytes uint8 / tok_off int32
+    [vocab + 1] the tokens' bytes, stop_ids int32 -> int32 [n_states, ceil(vocab / 32)] whose
+    bit (q, v) says that token v may be drawn in state q (a stop id: in accepting states)."""
+    L = _lib.load()
+    _require_cuda(trans, accept, tok_bytes, tok_off, stop_ids)
+    if trans.dtype != torch.int16 or trans.dim() != 2 or trans.shape[1] != 256 \
+            or not trans.is_contiguous():
+        raise CSError("trans must be a contiguous int16 [n_states, 256] tensor")
+    n_states = trans.shape[0]
+    if accept.dtype != torch.uint8 or tuple(accept.shape) != (n_states,) \
+            or not accept.is_contiguous():
+        raise CSError(f"accept must be a contiguous uint8 tensor of shape [{n_states}]")
+    if tok_off.dtype != torch.int32 or tok_off.dim() != 1 or tok_off.numel() < 2 \
+            or not tok_off.is_contiguous():
+        raise CSError("tok_off must be a contiguous int32 [vocab + 1] tensor")
+    if tok_bytes.dtype != torch.uint8 or tok_bytes.dim() != 1 or not tok_bytes.is_contiguous():
+        raise CSError("tok_bytes must be a contiguous 1-D uint8 tensor")
+    vocab = tok_off.numel() - 1
+    masks = torch.empty((n_states, (vocab + 31) // 32), dtype=torch.int32, device=trans.device)
+    rc = L.cs_dfa_token_masks(trans.data_ptr(), accept.data_ptr(), n_states, tok_bytes.data_ptr(),
+                              tok_off.data_ptr(), vocab, *_id_list(stop_ids, "stop_ids"),
+                              masks.data_ptr(), _stream())
+    _lib.check(rc, "cs_dfa_token_masks")
+    return masks
+
+
+def _mask_args(masks: Optional[torch.Tensor], dfa_state: Optional[torch.Tensor], rows: int,
+               n_states: Optional[int]):
+    """(masks pointer, mask_words, n_states, dfa_state pointer) of the *_dfa entries; masks
+    None: all NULL / 0, which makes the entry its *_ex sibling."""
+    if masks is None:
+        return None, 0, 0, None
+    if masks.dtype != torch.int32 or masks.dim() != 2 or not masks.is_contiguous():
+        raise CSError("masks must be a contiguous int32 [n_states, mask_words] tensor")
+    return (masks.data_ptr(), masks.shape[1], masks.shape[0] if n_states is None else int(n_states),
+            _state_ptr(dfa_state, "dfa_state", torch.int32, (rows,)))
+
+
+def vocab_sample_dfa(logits: torch.Tensor, seeds: Optional[torch.Tensor], *,
+                     masks: Optional[torch.Tensor] = None,
+                     dfa_state: Optional[torch.Tensor] = None, n_states: Optional[int] = None,
+                     temperature: float = 1.0, vocab: Optional[int] = None, softcap: float = 0.0,
+                     bias_ids: Optional[torch.Tensor] = None, bias_value: float = -1e6,
+                     repetition_penalty: float = 1.0, seen_ids: Optional[torch.Tensor] = None,
+                     seen_off: Optional[torch.Tensor] = None, n_draw: Optional[int] = None,
+                     workspace: Optional[Workspace] = None):
+    """``vocab_sample_ex`` on rows held to an automaton (cs_vocab_sample_dfa): row r may draw
+    the tokens whose bit is set in masks[dfa_state[r]] (``dfa_token_masks``; dfa_state int32
+    [rows]); the others are out of the draw and of the log-probabilities' normaliser.  A row
+    whose state allows nothing yields id -1.  masks None: ``vocab_sample_ex``, bit for bit."""
+    def controls(rows):
+        return (*_id_list(bias_ids, "bias_ids"), float(bias_value), float(repetition_penalty),
+                *_seen_args(seen_ids, seen_off, rows), *_mask_args(masks, dfa_state, rows, n_states))
+
+    return _vocab_sample("cs_vocab_sample_dfa", logits, seeds, n_draw, temperature, vocab, softcap,
+                         workspace, (bias_ids, seen_ids, seen_off, masks, dfa_state), controls)
+
+
+def sample_step_dfa(logits: torch.Tensor, base_seeds: Optional[torch.Tensor], step: torch.Tensor,
+                    done: torch.Tensor, out_len: torch.Tensor, out_tokens: torch.Tensor,
+                    next_tok: torch.Tensor, n_alive: torch.Tensor, *, pad_id: int,
+                    masks: Optional[torch.Tensor] = None, trans: Optional[torch.Tensor] = None,
+                    dfa_state: Optional[torch.Tensor] = None, n_states: Optional[int] = None,
+                    **kw) -> None:
+    """``sample_step_ex`` (whose keywords it takes) with every stream held to an automaton
+    (cs_sample_step_dfa): the draw is ``vocab_sample_dfa``'s in state dfa_state[s] (int32
+    [S], device, the start states before the first step), and an appended token's bytes
+    (tok_bytes / tok_off, needed here with or without stop strings) are walked through trans
+    (int16 [n_states, 256]) to the stream's next state, inside the same two launches.
+    masks None: ``sample_step_ex``, bit for bit."""
+    if masks is not None and trans is not None and (
+            trans.dtype != torch.int16 or trans.dim() != 2 or trans.shape[1] != 256
+            or not trans.is_contiguous()):
+        raise CSError("trans must be a contiguous int16 [n_states, 256] tensor")
+    if masks is not None and trans is not None and n_states is None \
+            and trans.shape[0] != masks.shape[0]:
+        raise CSError("trans and masks disagree on the number of states")
+    sample_step_ex(logits, base_seeds, step, done, out_len, out_tokens, next_tok, n_alive,
+                   pad_id=pad_id, _dfa=(masks, trans, dfa_state, n_states), **kw)
 
 
 class AttnPlan:

@@ -32,6 +32,7 @@ Seed semantics of the local samplers (the replacement for the remote API's
 """
 from __future__ import annotations
 
+import collections
 import logging
 import os
 import re
@@ -448,13 +449,126 @@ def _ragged_i32(lists, dev):
             torch.tensor(off, dtype=torch.int32, device=dev))
 
 
+# --- constrained sampling -----------------------------------------------------------
+class Constraint:
+    """What compile_constraint returns: an automaton over the text's bytes (one table, one
+    start state per pattern), the stop ids it was built for and the tokenizer's byte table;
+    the device copies (token masks, transitions, byte table) are built on first use, once per
+    device and vocabulary size."""
+
+    def __init__(self, dfa, starts: List[int], stop_ids: Tuple[int, ...], tok_bytes, tok_off,
+                 shared: Optional[dict] = None) -> None:
+        self.dfa, self.starts, self.stop_ids = dfa, list(starts), tuple(stop_ids)
+        self._bytes, self._off = tok_bytes, tok_off
+        self._dev = {} if shared is None else shared
+
+    def select(self, k: int) -> "Constraint":
+        """The constraint of pattern k alone (the same tables, one start state)."""
+        return Constraint(self.dfa, [self.starts[k]], self.stop_ids, self._bytes, self._off,
+                          self._dev)
+
+    def token_bytes(self, v: int) -> bytes:
+        """Token v's bytes (none for a special token or an id past the table)."""
+        return self._bytes[self._off[v]:self._off[v + 1]] if 0 <= v < len(self._off) - 1 else b""
+
+    def advance(self, state: int, v: int) -> int:
+        """The state after token v (the walk of cs_sample_step_dfa)."""
+        return self.dfa.walk(state, self.token_bytes(v))
+
+    def device(self, dev, vocab: int):
+        """(masks, trans, tok_bytes, tok_off) on ``dev`` for a model of ``vocab`` ids; ids past
+        the tokenizer's table have no bytes, so they are never drawable."""
+        key = (str(dev), int(vocab))
+        if key not in self._dev:
+            import numpy as np
+            n = len(self._off) - 1
+            off = np.full(vocab + 1, self._off[min(n, vocab)], dtype=np.int32)
+            off[:min(n, vocab) + 1] = self._off[:min(n, vocab) + 1]
+            data = np.frombuffer(bytes(self._bytes) + b"\0", dtype=np.uint8).copy()
+            tb, to = torch.from_numpy(data).to(dev), torch.from_numpy(off).to(dev)
+            trans = torch.from_numpy(self.dfa.trans.copy()).to(dev)
+            accept = torch.from_numpy(self.dfa.accept.astype(np.uint8)).to(dev)
+            stop = [i for i in self.stop_ids if 0 <= i < vocab]
+            stop_t = torch.tensor(stop, dtype=torch.int32, device=dev) if stop else None
+            self._dev[key] = (ops.dfa_token_masks(trans, accept, tb, to, stop_t), trans, tb, to)
+        return self._dev[key]
+
+
+def _spec_dfa(spec):
+    """(cache key, Dfa) of one constraint spec: a regex, a Dfa or {"type": "json_object"}."""
+    from . import constrain
+    if isinstance(spec, constrain.Dfa):
+        return ("dfa", spec.key()), spec
+    if isinstance(spec, str):
+        return ("re", spec), constrain.compile_regex(spec)
+    if isinstance(spec, dict):
+        if spec.get("type") != "json_object" or set(spec) - {"type", "max_depth"}:
+            raise ValueError(f"unsupported constraint {spec!r}: only "
+                             '{"type": "json_object"} (with an optional "max_depth")')
+        depth = int(spec.get("max_depth", 2))
+        return ("json", depth), constrain.json_object(depth)
+    raise TypeError(f"a constraint is a regex string, a Dfa or a dict, not {type(spec).__name__}")
+
+
+_SPEC_CACHE = 32
+
+
+def compile_constraint(tok, spec, stop_ids: Optional[Sequence[int]] = None) -> Constraint:
+    """The sampling constraint of ``spec`` for tokenizer ``tok``: a regex string
+    (constrain.compile_regex: full match), a constrain.Dfa, {"type": "json_object"} (one JSON
+    object, constrain.json_object(2)), or a list of those, one per prompt of generate_streams
+    (joined into one table by constrain.union).  ``stop_ids`` (default tok.eos_ids) are the
+    ids that may end a stream, drawable in accepting states only; generate / generate_streams
+    must be called with the same ones.
+
+    Built once per (tokenizer, spec, stop ids).  The tokenizer's exact token_bytes() table is
+    required (CharTokenizer and byte-level BPETokenizer have one): without it CSError, since a
+    constraint that silently did nothing would be worse than none."""
+    from . import constrain
+    tb = tok.token_bytes() if hasattr(tok, "token_bytes") else None
+    if tb is None:
+        raise ops.CSError(f"compile_constraint: {type(tok).__name__} has no exact token_bytes() "
+                          "table, so a token's effect on the pattern cannot be known")
+    stop = tuple(int(i) for i in (tok.eos_ids if stop_ids is None else stop_ids))
+    many = isinstance(spec, (list, tuple))
+    keyed = [_spec_dfa(s) for s in (spec if many else [spec])]
+    if not keyed:
+        raise ValueError("compile_constraint: an empty list of patterns")
+    key = (many, tuple(k for k, _ in keyed), tuple(sorted(set(stop))))
+    cache = tok.__dict__.setdefault("_constraints", collections.OrderedDict())
+    if key not in cache:
+        if many:
+            dfa, starts = constrain.union([d for _, d in keyed])
+        else:
+            dfa, starts = keyed[0][1], [keyed[0][1].start]
+        cache[key] = Constraint(dfa, starts, stop, bytes(tb[0]), [int(o) for o in tb[1]])
+        while len(cache) > _SPEC_CACHE:
+            cache.popitem(last=False)
+    return cache[key]
+
+
+def _constraint_starts(constraint: Constraint, stop: Sequence[int], n_prompts: int) -> List[int]:
+    """One start state per prompt, after checking that the masks were built for ``stop``."""
+    if not isinstance(constraint, Constraint):
+        raise TypeError("constraint must come from runtime.compile_constraint")
+    if set(constraint.stop_ids) != set(int(i) for i in stop):
+        raise ops.CSError("the constraint was compiled for other stop ids than this call uses: "
+                          "pass the same stop_ids to compile_constraint")
+    if len(constraint.starts) == 1:
+        return constraint.starts * n_prompts
+    if len(constraint.starts) != n_prompts:
+        raise ValueError(f"{len(constraint.starts)} patterns for {n_prompts} prompts")
+    return list(constraint.starts)
+
+
 # --- seeded generation on the engine ------------------------------------------------
 @torch.no_grad()
 def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int],
              seeds: Sequence[Optional[int]], max_tokens: int, temperature: float = 1.0,
              bias_ids: Sequence[int] = (), bias_value: float = -1e6,
              stop_ids: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
-             stop_strings: Optional[Sequence[str]] = None) -> List[List[int]]:
+             stop_strings: Optional[Sequence[str]] = None,
+             constraint: Optional[Constraint] = None) -> List[List[int]]:
     """Sample len(seeds) continuations of one prefix in a batch (token t of stream i
     drawn with seed draw_seed(seeds[i], t)); a stream stops after a stop token (not
     included) or max_tokens tokens.
@@ -463,7 +577,13 @@ def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int
     stream's own tokens (ops.vocab_sample_ex: the row transform of the device loop), and a
     stream also ends with the token that completes one of early_stop_strings(stop_strings)
     (included, so the caller's cut sees it).  With the defaults the draws are
-    ops.vocab_sample's as before."""
+    ops.vocab_sample's as before.
+
+    ``constraint`` (compile_constraint, one pattern) holds every stream to its automaton:
+    the state is kept here on the host and each draw is ops.vocab_sample_dfa's, so only
+    tokens whose bytes keep the pattern alive are drawn, and a stop token only where the text
+    matches.  A stream that no token can continue ends there; one that reaches max_tokens
+    before the pattern is complete returns its prefix, which does not match."""
     n = len(seeds)
     seeds = [fresh_seed() if s is None else int(s) for s in seeds]
     stop = set(tok.eos_ids if stop_ids is None else stop_ids)
@@ -475,10 +595,14 @@ def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int
     alive = list(range(n))          # stream ids, in beam order
     dev = engine.device
     temperature, penalty = float(temperature), float(repetition_penalty)
-    controls = temperature == 0.0 or penalty != 1.0
+    controls = temperature == 0.0 or penalty != 1.0 or constraint is not None
     stops = early_stop_strings(stop_strings)
     table = stop_token_table(tok, engine.model.cfg.vocab) if stops else None
     tails = [b""] * n
+    dfa = {}
+    if constraint is not None:
+        states = _constraint_starts(constraint, stop, 1) * n
+        dfa["masks"] = constraint.device(dev, engine.model.cfg.vocab)[0]
     bias_t = torch.tensor(list(bias_ids), dtype=torch.int32, device=dev) \
         if controls and len(bias_ids) else None
     prefix_ids = list(prefix_ids)
@@ -491,19 +615,24 @@ def generate(engine: ScoringEngine, tok: CharTokenizer, prefix_ids: Sequence[int
         if controls:
             seen_ids, seen_off = _ragged_i32([prefix_ids + out[i] for i in alive], dev) \
                 if penalty != 1.0 else (None, None)
-            ids, _ = ops.vocab_sample_ex(logits, sd, temperature=temperature,
-                                         softcap=engine.softcap, bias_ids=bias_t,
-                                         bias_value=float(bias_value), repetition_penalty=penalty,
-                                         seen_ids=seen_ids, seen_off=seen_off)
+            if constraint is not None:
+                dfa["dfa_state"] = torch.tensor([states[i] for i in alive], dtype=torch.int32,
+                                                device=dev)
+            draw = ops.vocab_sample_ex if constraint is None else ops.vocab_sample_dfa
+            ids, _ = draw(logits, sd, temperature=temperature, softcap=engine.softcap,
+                          bias_ids=bias_t, bias_value=float(bias_value),
+                          repetition_penalty=penalty, seen_ids=seen_ids, seen_off=seen_off, **dfa)
         else:
             logits = apply_bias(logits, bias_ids, bias_value)
             ids, _ = ops.vocab_sample(logits, sd, temperature=temperature, softcap=engine.softcap)
         ids = ids[:, 0].tolist()
         parent, toks, nxt = [], [], []
         for j, (i, v) in enumerate(zip(alive, ids)):
-            if v in stop:
+            if v in stop or v < 0:          # -1: the pattern allows no token here
                 continue
             out[i].append(v)
+            if constraint is not None:
+                states[i] = constraint.advance(states[i], v)
             if table is not None:
                 hit, tails[i] = stop_window_push(tails[i], table[v], stops)
                 if hit:
@@ -538,7 +667,8 @@ def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
                      bias_value: float = -1e6, stop_ids: Optional[Sequence[int]] = None,
                      poll_every: int = 8, return_logprobs: bool = False,
                      repetition_penalty: float = 1.0,
-                     stop_strings: Optional[Sequence[str]] = None):
+                     stop_strings: Optional[Sequence[str]] = None,
+                     constraint: Optional[Constraint] = None):
     """Sample continuations of many prompts at once with the loop closed on the device:
     result[p][i] = the tokens of prompt p under seeds[p][i] (``seeds``: one list used for
     every prompt, or one list per prompt, of any lengths), drawn as ``generate`` draws
@@ -556,7 +686,12 @@ def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
     extends by the tokens generated so far, and a stream ends with the token whose bytes
     complete one of early_stop_strings(stop_strings) -- where the tokenizer has an exact
     token_bytes() table; otherwise the streams run on to a stop token or max_tokens as
-    before.  With the defaults the step is cs_sample_step."""
+    before.  With the defaults the step is cs_sample_step.
+
+    ``constraint`` (compile_constraint: one pattern for every prompt, or one per prompt) is
+    ``generate``'s, with each stream's automaton state kept on the device and advanced inside
+    the step (cs_sample_step_dfa), so the graph replays as before.  A stream cut at
+    max_tokens returns a prefix that does not match yet."""
     from .engine import DecodeState
     P = len(prefixes)
     per = _seed_lists(seeds, P)
@@ -610,7 +745,17 @@ def generate_streams(engine: ScoringEngine, tok: CharTokenizer,
                     ex.update(tok_bytes=tables[0], tok_off=tables[1],
                               tail=torch.zeros(S, ops.MAX_STOP_LEN, dtype=torch.uint8, device=dev),
                               tail_len=torch.zeros(S, dtype=torch.int32, device=dev))
-            step_op = ops.sample_step_ex if ex else ops.sample_step
+            if constraint is not None:
+                starts = _constraint_starts(constraint, stop, P)
+                masks, trans, tb, to = constraint.device(dev, m.cfg.vocab)
+                ex.setdefault("repetition_penalty", penalty)
+                # the constraint's byte table serves the stop strings too: a token without
+                # bytes is never drawn under a constraint
+                ex.update(masks=masks, trans=trans, tok_bytes=tb, tok_off=to,
+                          dfa_state=torch.tensor([starts[p] for p in range(P) for _ in range(B)],
+                                                 dtype=torch.int32, device=dev))
+            step_op = ops.sample_step_dfa if constraint is not None else \
+                ops.sample_step_ex if ex else ops.sample_step
 
             def post():
                 logits = m.lm_head(ds.hidden)                      # [S, V]

@@ -591,9 +591,22 @@ def get_token_ids(model, text) -> Dict[str, int]:
         return {}
 
 
+def _constraint(tok, pattern, response_format):
+    """The runtime constraint of generate_text(s)' ``pattern`` / ``response_format``, or None."""
+    if pattern is not None and response_format is not None:
+        raise ValueError("give pattern or response_format, not both")
+    if response_format is not None:
+        if not isinstance(response_format, dict) or response_format != {"type": "json_object"}:
+            raise ValueError(f"unsupported response_format {response_format!r}: only "
+                             '{"type": "json_object"}')
+        return runtime.compile_constraint(tok, {"type": "json_object"})
+    return None if pattern is None else runtime.compile_constraint(tok, pattern)
+
+
 def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, temperature=1,
                   terminators=(), seed=None, bias_against_tokens=None, bias_value=-1000000,
-                  use_chat_completions=True, repetition_penalty=1.0) -> str:
+                  use_chat_completions=True, repetition_penalty=1.0, pattern=None,
+                  response_format=None) -> str:
     """Sample a completion locally (src/utils.py:77-198 contract; '[ERROR: ...]' on failure).
 
     Chat mode renders the chat template with the generation prompt; completions mode
@@ -601,9 +614,16 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
     draw_seed(seed, t); stop tokens end the text and are not included.  temperature 0
     decodes greedily, repetition_penalty is transformers' rule over the prompt's and the
     generated tokens, and a terminator ends the decoding where it can (runtime.generate);
-    the cut below decides the returned text in every case."""
+    the cut below decides the returned text in every case.
+
+    ``pattern`` (a regex of constrain.compile_regex's subset, matched against the whole
+    completion) or ``response_format={"type": "json_object"}`` (the hosted API's spelling: the
+    completion is one JSON object) constrain the decoding itself; giving both, or another
+    response format, is a ValueError and so an '[ERROR: ValueError]' string.  A completion cut
+    at max_tokens is a prefix of a match, not a match."""
     try:
         engine, tok = runtime.get_engine(model)
+        constraint = _constraint(tok, pattern, response_format)
         if use_chat_completions:
             ids, _ = tok.render_chat(system_prompt or None, user_prompt)
         else:
@@ -614,7 +634,7 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
             out = runtime.generate(engine, tok, ids, [seed], max_tokens, float(temperature),
                                    bias_ids=bias, bias_value=float(bias_value),
                                    repetition_penalty=float(repetition_penalty),
-                                   stop_strings=terminators)[0]
+                                   stop_strings=terminators, constraint=constraint)[0]
         text = tok.decode(out)
         for term in terminators or ():
             cut = text.find(term)
@@ -629,14 +649,15 @@ def generate_text(model, user_prompt, system_prompt=None, max_tokens=4096, tempe
 def generate_texts(model, user_prompts, system_prompts=None, n_per_prompt=1, max_tokens=4096,
                    temperature=1, terminators=(), seeds=None, bias_against_tokens=None,
                    bias_value=-1000000, use_chat_completions=True,
-                   repetition_penalty=1.0) -> List[List[str]]:
+                   repetition_penalty=1.0, pattern=None, response_format=None) -> List[List[str]]:
     """The batch form of generate_text: result[p][i] = completion i of prompt p, every prompt
     and sample decoded together on the device (runtime.generate_streams; bf16 engines).
 
     system_prompts: None, one string for every prompt, or one per prompt.  seeds: None
     (fresh seeds), one list of n_per_prompt seeds used for every prompt, or one list per
     prompt.  Rendering, the terminator cut and the '[ERROR: ...]' contract are generate_text's:
-    a failure puts the error string in every slot."""
+    a failure puts the error string in every slot.  ``pattern`` and ``response_format`` are
+    generate_text's; ``pattern`` may also be a list with one regex per prompt."""
     users = list(user_prompts)
     P = len(users)
     n = int(n_per_prompt)
@@ -664,11 +685,12 @@ def generate_texts(model, user_prompts, system_prompts=None, n_per_prompt=1, max
                 ids = tok.render_raw(f"{sysp}\n\n{user}" if sysp else f"{user}")
             idss.append(ids)
         bias = runtime.bias_token_ids(tok, bias_against_tokens)
+        constraint = _constraint(tok, pattern, response_format)
         outs = runtime.generate_streams(engine, tok, idss, [None] * n if seeds is None else seeds,
                                         max_tokens, float(temperature), bias_ids=bias,
                                         bias_value=float(bias_value),
                                         repetition_penalty=float(repetition_penalty),
-                                        stop_strings=terminators)
+                                        stop_strings=terminators, constraint=constraint)
         texts = []
         for row in outs:
             texts.append([])

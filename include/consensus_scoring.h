@@ -382,6 +382,80 @@ int cs_sample_step_ex(const void* logits, int dtype, int64_t S, int64_t vocab, i
                       size_t workspace_bytes, cs_stream_t stream);
 
 /*
+ * cs_dfa_token_masks — which tokens a byte-level automaton lets a stream draw, per state.
+ *
+ * trans is int16 [n_states][256] (the next state on a byte, -1: dead), accept uint8 [n_states],
+ * token v's bytes are tok_bytes[tok_off[v] : tok_off[v+1]] (the table of cs_sample_step_ex),
+ * all device memory.  masks is uint32 [n_states][ceil(vocab / 32)]; bit v & 31 of word
+ * masks[q][v >> 5] is set iff
+ *   v is listed in stop_ids (n_stop <= 16): accept[q] != 0 (the text may end here);
+ *   otherwise: token v has at least one byte and walking its bytes from q never reaches -1
+ *     (nor a value >= n_states, which counts as dead).
+ * Bits past vocab are 0.  One launch, every word written; n_states * vocab / 8 bytes.
+ * 1 <= n_states <= 1024, 0 < vocab < 2^31.
+ */
+int cs_dfa_token_masks(const int16_t* trans, const uint8_t* accept, int32_t n_states,
+                       const uint8_t* tok_bytes, const int32_t* tok_off, int64_t vocab,
+                       const int32_t* stop_ids, int32_t n_stop, uint32_t* masks,
+                       cs_stream_t stream);
+
+/*
+ * cs_vocab_sample_dfa — cs_vocab_sample_ex on rows constrained by an automaton.
+ *
+ * Row r is in state dfa_state[r] (int32, device).  After bias, soft-cap and penalty, a token
+ * whose bit is clear in masks[dfa_state[r] * mask_words + ...] (the layout of
+ * cs_dfa_token_masks with row stride mask_words >= ceil(vocab / 32)) has x = -inf: it is out
+ * of the log-sum-exp, so out_lp is the log-probability under the constrained distribution, and
+ * by the never-drawn rule it is never drawn; a NaN logit under a clear bit does not poison the
+ * row.  A state outside [0, n_states) allows nothing: id -1, NaN.  The bits are read from
+ * global memory (the two LDS bitmaps of cs_vocab_sample_ex stay as they are, so the limits do).
+ * masks == NULL: the call IS cs_vocab_sample_ex (same kernels, same bits; mask_words,
+ * n_states and dfa_state are not looked at).  Otherwise 1 <= n_states <= 1024.
+ */
+size_t cs_vocab_sample_dfa_workspace_size(int64_t rows, int64_t vocab, int32_t n_draw);
+int cs_vocab_sample_dfa(const void* logits, int dtype, int64_t rows, int64_t vocab, int64_t ld,
+                        float temperature, float softcap, const uint64_t* seeds, int32_t n_draw,
+                        const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                        float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                        const uint32_t* masks, int64_t mask_words, int32_t n_states,
+                        const int32_t* dfa_state, int32_t* out_ids, float* out_lp, void* workspace,
+                        size_t workspace_bytes, cs_stream_t stream);
+
+/*
+ * cs_sample_step_dfa — cs_sample_step_ex with every stream held to an automaton; still two
+ * launches, and still replayable from a captured graph with no new argument.
+ *
+ * For an unfinished stream s the draw is cs_vocab_sample_dfa's in state dfa_state[s], and the
+ * state update is cs_sample_step_ex's.  Then, if the token was appended, its bytes
+ * (tok_bytes / tok_off, needed here whether or not stop strings are given) are walked from
+ * dfa_state[s] through trans (int16 [n_states][256]) and dfa_state[s] becomes the state
+ * reached (-1 if the walk dies, which a set mask bit rules out); a token with no bytes leaves
+ * it.  A state with no drawable token gives id -1, which ends the stream like any row without
+ * a drawable logit; a stop id is drawable in accepting states only (cs_dfa_token_masks) and
+ * ends the stream as before.
+ * masks == NULL: the call IS cs_sample_step_ex (same kernels, same bits).
+ * Limits and workspace: those of cs_sample_step_ex, 1 <= n_states <= 1024.
+ *
+ * Replaces: response_format={"type": "json_object"} of the evaluator's judges
+ *   (src/evaluation.py:413-893) and the answer format the Habermas Machine parses
+ *   (src/methods/habermas_machine.py), which the hosted endpoint enforces or the caller
+ *   re-parses.
+ */
+size_t cs_sample_step_dfa_workspace_size(int64_t S, int64_t vocab);
+int cs_sample_step_dfa(const void* logits, int dtype, int64_t S, int64_t vocab, int64_t ld,
+                       float temperature, float softcap, const uint64_t* base_seeds,
+                       const int32_t* step, const int32_t* bias_ids, int32_t n_bias, float bias_value,
+                       float repetition_penalty, const int32_t* seen_ids, const int32_t* seen_off,
+                       const int32_t* stop_ids, int32_t n_stop, const uint8_t* tok_bytes,
+                       const int32_t* tok_off, const uint8_t* stop_bytes, const int32_t* stop_off,
+                       int32_t n_stop_seq, uint8_t* tail, int32_t* tail_len, const uint32_t* masks,
+                       int64_t mask_words, const int16_t* trans, int32_t n_states,
+                       int32_t* dfa_state, int32_t max_tokens, int32_t pad_id, int32_t* done,
+                       int32_t* out_len, int32_t* out_tokens, float* out_lp, int64_t* next_tok,
+                       int32_t* n_alive, void* workspace, size_t workspace_bytes,
+                       cs_stream_t stream);
+
+/*
  * cs_prefix_attention — cascade attention of many candidate streams over SHARED
  * per-agent prefix K/V (bf16 in / bf16 out, fp32 online softmax, bf16 MFMA).
  *
