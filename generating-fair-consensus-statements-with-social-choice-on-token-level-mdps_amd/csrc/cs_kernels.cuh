@@ -327,7 +327,22 @@ __device__ __forceinline__ void lse_accum(float& m, float& s, const float* v) {
 #pragma unroll
   for (int i = 1; i < N; ++i) cm = fmaxf(cm, v[i]);
   const float mn = fmaxf(m, cm);
-  if (mn == -INFINITY) return;
+  if (mn == -INFINITY) {
+    // Empty state, and nothing in v above -inf.  fmaxf skips a NaN, so v may hold one; it must
+    // poison the row (a row with a NaN has a NaN lse).  Every element here is -inf or NaN, so
+    // their sum is NaN exactly when one of them is.  (0, NaN) survives every later accum and
+    // merge, also beside empty partners, where (-inf, NaN) would be dropped by lse_merge's own
+    // early return.  This rare branch is the only place a NaN can get lost: with a finite mn it
+    // goes through exp2 into s.  NaN-free rows never change here.
+    float t = v[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i) t += v[i];
+    if (t != t) {
+      m = 0.0f;
+      s = t;
+    }
+    return;
+  }
   const float off = mn * kLog2e;
   float acc = 0.0f;
 #pragma unroll

@@ -317,9 +317,9 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(
       }
     }
   }
-  // lse_accum drops a NaN that arrives while (m, s) is still empty (fmaxf(-inf, NaN) is
-  // -inf), but a NaN token must poison the row's lse wherever it sits: (0, NaN) survives
-  // every merge, also with empty partners
+  // a NaN token must poison the row's lse wherever it sits, also one that arrives while
+  // (m, s) is still empty (lse_accum leaves (0, NaN) then; saw_nan does not depend on it):
+  // (0, NaN) survives every merge, also with empty partners
   if (saw_nan) {
     if (m == -INFINITY) m = 0.0f;
     s = __builtin_nanf("");

@@ -74,6 +74,13 @@ size_t cs_workspace_size(int64_t rows, int64_t vocab, int32_t k);
  * src/utils.py:262-263, which every caller filters).
  * One HBM pass over the logits; fp32 accumulation.
  *
+ * Non-finite rows.  A row with a NaN anywhere in its first `vocab` columns has NaN
+ * lse and NaN out_tok_lp at every j, in every dtype, soft-cap mode and split plan
+ * (as the fp64 oracle, oracle_logsoftmax_gather).  A row whose first `vocab` columns
+ * are all -inf (softcap = 0) has lse = -inf and NaN out_tok_lp, like torch.logsumexp;
+ * the fp64 oracle returns NaN for the lse of such a row as well.  The same holds for
+ * the agent rows of cs_beam_step and cs_beam_decode_step, which share this stream.
+ *
  * Replaces: the remote log-softmax + gather behind get_prompt_logprobs
  *   (src/utils.py:249-263, echo=True prompt log-probs), the per-token read in
  *   _get_agent_token_logprob (src/methods/beam_search.py:389-390; one row per
