@@ -933,8 +933,9 @@ BeamCounters beam_counters(char* wsb) {
 void beam_sort_after(hipStream_t st, const float* W, int64_t C, int32_t n2, int32_t n_order,
                      int32_t* out_order, float* out_order_val) {
   if (n_order > 0 && n2 > kFusedSort)
-    hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(256), static_cast<size_t>(n2) * sizeof(unsigned long long),
-                       st, W, static_cast<int32_t>(C), C, n2, n_order, out_order, out_order_val);
+    launch_big_lds<&topk_kernel>(kTopkLdsMax, dim3(1), dim3(256),   // B*K > 8192: 128 KiB
+                                 static_cast<size_t>(n2) * sizeof(unsigned long long), st, W,
+                                 static_cast<int32_t>(C), C, n2, n_order, out_order, out_order_val);
 }
 }  // namespace
 

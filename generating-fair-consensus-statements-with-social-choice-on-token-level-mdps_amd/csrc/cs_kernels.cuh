@@ -707,6 +707,8 @@ inline SplitPlan plan_split(int64_t rows, int64_t vocab, int dtype) {
 // candidate proposer: vocab top-k and seeded Gumbel-max sampling
 // ---------------------------------------------------------------------------
 constexpr int kTopkChunk = 4096;   // vocab elements sorted per (row, chunk) workgroup
+// the dynamic LDS of the largest sort of topk_kernel and vocab_topk_merge_kernel: 16384 keys
+constexpr size_t kTopkLdsMax = 16384 * sizeof(unsigned long long);
 constexpr int kMaxDraws = 16;
 
 __device__ __forceinline__ float key_to_float(uint32_t key) {

@@ -174,9 +174,11 @@ int cs_segmented_topk(const float* W, int32_t n_seg, int32_t seg_len, int64_t ld
   }
   int32_t n2 = 2;
   while (n2 < seg_len) n2 <<= 1;
-  hipLaunchKernelGGL(topk_kernel, dim3(static_cast<uint32_t>(n_seg)), dim3(256),
-                     static_cast<size_t>(n2) * sizeof(unsigned long long),
-                     static_cast<hipStream_t>(stream), W, seg_len, ld, n2, k, out_idx, out_val);
+  // seg_len > 8192: 128 KiB of dynamic LDS
+  launch_big_lds<&topk_kernel>(kTopkLdsMax, dim3(static_cast<uint32_t>(n_seg)), dim3(256),
+                               static_cast<size_t>(n2) * sizeof(unsigned long long),
+                               static_cast<hipStream_t>(stream), W, seg_len, ld, n2, k, out_idx,
+                               out_val);
   return check_launch("cs_segmented_topk");
 }
 

@@ -913,9 +913,11 @@ int cs_vocab_topk(const void* logits, int dtype, int64_t rows, int64_t vocab, in
   });
   const int32_t n2 = next_pow2(nkeys);
   const int32_t lds_keys = n2 > kTopkChunk ? n2 : kTopkChunk;
-  hipLaunchKernelGGL(vocab_topk_merge_kernel, dim3(static_cast<uint32_t>(rows)), dim3(256),
-                     static_cast<size_t>(lds_keys) * sizeof(unsigned long long), st, part,
-                     static_cast<int32_t>(nkeys), n2, k, out_ids, out_vals);
+  // up to 16384 keys: 128 KiB of dynamic LDS
+  launch_big_lds<&vocab_topk_merge_kernel>(kTopkLdsMax, dim3(static_cast<uint32_t>(rows)), dim3(256),
+                                           static_cast<size_t>(lds_keys) * sizeof(unsigned long long),
+                                           st, part, static_cast<int32_t>(nkeys), n2, k, out_ids,
+                                           out_vals);
   return check_launch("cs_vocab_topk");
 }
 

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from topk_ref import decode_kp as _decode_kp, plan_nsplit as _plan_nsplit
+
 pytestmark = pytest.mark.gpu
 
 LP_TOL = 1e-3
@@ -687,25 +689,6 @@ def test_beam_decode_fuzz(ops, orc, dev, i, dtype, A, B, K, vocab, softcap, kind
 # --- every compiled instantiation of the two beam kernels, and cs_beam_step with K > 1024 ---
 def _eq_nan(a: torch.Tensor, b: torch.Tensor) -> bool:
     return torch.equal(torch.nan_to_num(a, nan=7.0), torch.nan_to_num(b, nan=7.0))
-
-
-def _plan_nsplit(rows: int, vocab: int, dtype) -> int:
-    """The library's split plan (cs_kernels.cuh plan_split), restated on the CPU."""
-    if rows >= 256:
-        return 1
-    grain = 256 * (4 if dtype == torch.float32 else 8)
-    want = min((1024 + rows - 1) // rows, max(vocab // (grain * 4), 1))
-    if want <= 1:
-        return 1
-    length = -(-(-(-vocab // want)) // grain) * grain
-    return max(-(-vocab // length), 1)
-
-
-def _decode_kp(B: int, vocab: int, K: int, dtype) -> int:
-    """Elements per lane of a proposer chunk (beam.hip decode_kp), restated on the CPU."""
-    big = 8 if dtype == torch.float32 else 16
-    nbig = B * -(-vocab // (big * 1024))
-    return 4 if nbig < 128 and -(-vocab // 4096) * K <= 16384 else big
 
 
 def _check_beam_step_is_unfused(ops, lg, tg, Rg, kind, softcap):

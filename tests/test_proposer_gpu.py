@@ -3,7 +3,21 @@ import numpy as np
 import pytest
 import torch
 
+import topk_ref
+
 pytestmark = pytest.mark.gpu
+
+
+def _check_capped(x, ids, vals, cap):
+    """What ties ids to values under a soft-cap: ids unique and in range, values non-increasing,
+    and each value the float64 cap of the element its id names, inside the fp32 cap's window."""
+    x = x.float().double().numpy()
+    ids, vals = ids.cpu().numpy(), vals.cpu().numpy().astype(np.float64)
+    assert ids.min() >= 0 and ids.max() < x.shape[1]
+    assert all(len(set(r)) == len(r) for r in ids.tolist())
+    assert (np.diff(vals, axis=1) <= 0).all()
+    ref = cap * np.tanh(np.take_along_axis(x, ids.astype(np.int64), axis=1) / cap)
+    assert (np.abs(vals - ref) <= topk_ref.cap_window(ref, cap)).all()
 
 
 @pytest.mark.parametrize("dtype,rows,vocab,k,softcap", [
@@ -28,6 +42,7 @@ def test_vocab_topk_matches_oracle(ops, orc, dev, dtype, rows, vocab, k, softcap
     if softcap:
         # fp32 tanh of the kernel vs torch may split a tie: require identical value multisets
         np.testing.assert_allclose(np.sort(vals.cpu().numpy(), 1), np.sort(o_vals, 1), atol=1e-5)
+        _check_capped(x, ids, vals, softcap)
     else:
         assert np.array_equal(got, o_ids)
         np.testing.assert_array_equal(vals.cpu().numpy(), o_vals.astype(np.float32))
@@ -65,6 +80,7 @@ def test_vocab_topk_edge_rows(ops, orc, dev, case):
     o_ids, o_vals = orc.vocab_topk(xf.double().numpy(), k)
     if cap:   # fp32 tanh of the kernel vs torch: compare value multisets, then ids by value
         np.testing.assert_allclose(vals.cpu().numpy(), o_vals, atol=1e-5)
+        _check_capped(xd, ids, vals, cap)
     else:
         assert np.array_equal(ids.cpu().numpy(), o_ids)
         np.testing.assert_array_equal(vals.cpu().numpy(), o_vals.astype(np.float32))
